@@ -2,6 +2,7 @@
 """Benchmark of the CLIP-FSAR episodic-inference hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--episodes-per-step B] [--precision bf16|fp16|fp16_strict|fp32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,14 +14,22 @@ Metric (BASELINE.json): episodes/sec, 5-way 1-shot, 8 frames, ViT-B/16 (config[1
 weights, synthetic frames).  One "step" = the full forward A0 -> A15 (+ top-1) over a batch of B synthetic episodes
 that are already resident in HBM.  Episodes shard over ranks with no data-path collective (weak scaling: every rank
 does K steps of B episodes); the only collective is ONE all-gather (RCCL) of the per-episode accuracies, inside the
-timed region.  Rank 0 prints ONE JSON line.
+timed region.  Rank 0 prints ONE JSON line: `metric`, `value` (episodes/s), `unit`, `higher_is_better`, `dtype` and
+`ms_per_step` (wall time of one timed step) are the headline.  A plain run does only what that line needs: set-up, W warm-up
+steps, K timed steps, the line.
 
-The line also carries
+--dump-outputs DIR  after the timed steps, rank 0 writes what its last timed step returned to a caller, as float32 .npy files:
+                    logits.npy [B, queries, way], class_logits.npy [B, support + queries, train classes] and top1.npy [B] (the
+                    per-episode top-1 accuracies).  Inputs and weights are seeded: the same arguments give the same inputs.
+--full              everything else the line has carried, each measured as before:
   roofline     -- for the dominant kernel (the bf16 MFMA GEMM): algorithmic FLOPs of its launches / their measured
                   duration (HIP events on the launch stream, recorded live during the timed steps), against the dense
-                  bf16 MFMA peak of MI355X (2.5 PFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md);
+                  bf16 MFMA peak of MI355X (2.5 PFLOP/s, MI355X datasheet);
+  parity       -- the first episode's logits against the reference-generated golden of the configuration;
+  fp16_mode, strict_mode, configs -- short timed legs of the other 16-bit modes and of cfg3 / cfg4 (default bf16 cfg2 run);
   cpu_baseline -- the CPU oracle (torch fp32 restatement of the reference path, oracle/clipfsar_oracle.py) timed on the
                   host cores of this box on a bounded sample (rank 0, N = 1 only).
+The --no-* switches below drop single pieces of a --full run.
 """
 from __future__ import annotations
 
@@ -360,10 +369,15 @@ def parse_args(argv=None):
                          "before every step (serial) and by the product harness's double-buffered copy stream (overlapped); `value` stays the "
                          "resident figure")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-fp16-leg", action="store_true", help="skip the extra fp16-mode and fp16_strict-mode measurements of the default (bf16) run")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the short cfg3 / cfg4 legs (bf16 and fp16) of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline (per-launch HIP events), golden parity, the fp16 / "
+                         "fp16_strict legs, the cfg3 / cfg4 legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits, class_logits, per-episode top-1) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: no HIP events around the GEMM launches, no roofline object")
+    ap.add_argument("--no-fp16-leg", action="store_true", help="--full: skip the extra fp16-mode and fp16_strict-mode measurements of the bf16 run")
+    ap.add_argument("--no-config-legs", action="store_true", help="--full: skip the short cfg3 / cfg4 legs (bf16 and fp16)")
     ap.add_argument("--dev-gemm-variant", default=None,
                     help="developer A/B only (needs CFSAR_DEV_LIB=1): 'variant[:dbg]' forced on every 16-bit GEMM, e.g. 13 = p12")
     ap.add_argument("--rendezvous-timeout", type=int, default=300,
@@ -373,7 +387,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo rehearsal of the launch + collective + timing protocol with a no-op step "
                          "(tests/test_distributed_gloo.py); prints a line marked dry_run, never a benchmark result")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _spawn_entry(local_rank, world, port, argv):
@@ -466,6 +483,7 @@ def run(args):
     ARCH, SHOT, T, MERGE_BEFORE, GFLOP_PER_FRAME = cfgsel["arch"], cfgsel["shot"], cfgsel["T"], cfgsel["merge_before"], cfgsel["gflop"]
     if args.config != "cfg2":
         args.no_cpu_baseline = True            # the CPU leg is defined on the headline config only
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -504,9 +522,11 @@ def run(args):
     B = args.episodes_per_step or default_episodes_per_step(args.config, dry)
     timer = None
     first_logits = {}
+    last = {}                                                        # what the last step returned (--dump-outputs)
     if dry:
         def step(i, acc_out):                                        # no-op stand-in: protocol rehearsal only
             acc_out[i * B:(i + 1) * B] = float(rank)
+            last["top1"] = acc_out[i * B:(i + 1) * B]
     else:
         from clip_fsar_amd import hip
         from clip_fsar_amd.engine import ClipFsarEngine
@@ -515,15 +535,20 @@ def run(args):
             v = [int(x) for x in (args.dev_gemm_variant.split(":") + ["0"])[:2]]
             hip.lib().cfsar_debug_set_gemm_variant(v[0], v[1])
         a = synth.ARCHS[ARCH]
-        # identical weights on every rank, built locally (no broadcast needed)
-        sd = {k: torch.from_numpy(v) for k, v in synth.head_state_dict(ARCH, SEED).items()}
+        # identical weights on every rank, built locally (no broadcast needed), and the synthetic episodes of this rank (episode ids e
+        # with e % world == rank).  Both are pure functions of their seeds; numpy releases the GIL in the generators, so a few threads
+        # build the same arrays several times faster than one.
+        npool = args.pool if args.pool > 0 else B
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(8) as ex:
+            sd_job = ex.submit(synth.head_state_dict, ARCH, SEED)
+            pool = list(ex.map(lambda i: synth.make_episode(WAY, SHOT, QPC, T, a["res"], N_TEST, rank + world * i, SEED), range(npool)))
+            sd = {k: torch.from_numpy(v) for k, v in sd_job.result().items()}
         tt = synth.text_features(N_TRAIN, a["embed"], "train", SEED)
         te = synth.text_features(N_TEST, a["embed"], "test", SEED)
         eng = ClipFsarEngine(a, sd, tt, te, precision=args.precision, device=dev, max_frames=max(1280, B * frames_per_ep))
-        # synthetic episodes of this rank (episode ids e with e % world == rank), resident in HBM before timing: every step holds B
-        # DISTINCT episodes (each uploaded once; the steps cycle through a few rotations of the pool)
-        npool = args.pool if args.pool > 0 else B
-        pool = [synth.make_episode(WAY, SHOT, QPC, T, a["res"], N_TEST, rank + world * i, SEED) for i in range(npool)]
+        # resident in HBM before timing: every step holds B DISTINCT episodes (each uploaded once; the steps cycle through a few
+        # rotations of the pool)
         keys = (("sup", "support_set"), ("tgt", "target_set"), ("sl", "support_labels"), ("rl", "real_support_labels"), ("tl", "target_labels"))
         dev_eps = [{k: torch.from_numpy(e[src]).to(dev) for k, src in keys} for e in pool]
         batches = []
@@ -532,17 +557,18 @@ def run(args):
             batches.append({k: torch.stack([e[k] for e in eps]) for k, _ in keys})
         del dev_eps
 
-        if rank == 0:                                                # per-launch events and the CPU leg: rank 0 only
+        if rank == 0 and full:                                       # per-launch events and the CPU leg: rank 0 only
             timer = GemmTimer(hip)
             timer.install()
 
         def step(i, acc_out):
             b = batches[i % len(batches)]
-            logits, _ = eng.forward(b["sup"], b["tgt"], b["sl"], b["rl"], way=WAY, T=T, merge_before=MERGE_BEFORE)
+            logits, class_logits = eng.forward(b["sup"], b["tgt"], b["sl"], b["rl"], way=WAY, T=T, merge_before=MERGE_BEFORE)
             # A17: per-episode top-1 accuracy (metrics.topks_correct semantics, reference utils/metrics.py:100-138)
             hip.episode_top1(logits, b["tl"], acc_out[i * B:(i + 1) * B])
             if i % len(batches) == 0:
                 first_logits["v"] = logits                           # batch 0, kept for the post-run parity check
+            last.update(logits=logits, class_logits=class_logits, top1=acc_out[i * B:(i + 1) * B])
 
     acc = torch.zeros(max(args.steps, args.warmup, 1) * B, device=dev)
     for i in range(args.warmup):
@@ -552,7 +578,7 @@ def run(args):
         _checkin("warm", rank, world, args.rendezvous_timeout)      # engines built, warm-up done on EVERY rank -- or say which is missing
         dist.barrier()
     sync()
-    # HIP events around every GEMM launch of the timed region (the roofline object).  Small batches run the tower as two concurrent
+    # --full: HIP events around every GEMM launch of the timed region (the roofline object).  Small batches run the tower as two concurrent
     # chains on two streams, where ~200 timing events per episode serialise the chains (measured: 3.97 -> 5.64 ms per episode):
     # there the events bracket the launches of every 5th step only; the value is still the time of ALL timed steps.
     event_every = 1 if (dry or B * frames_per_ep > 160) else 5
@@ -594,6 +620,13 @@ def run(args):
         collective = {"backend": dist.get_backend(), "rccl_world_size": int(gathered.numel() // max(1, args.steps * B)),
                       "gathered_elements": int(gathered.numel())}
 
+    if args.dump_outputs and rank == 0:                              # the last timed step's results, before anything else runs
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, v in last.items():
+            if v is not None:
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), v.detach().float().cpu().numpy())
+
     host_inputs = None
     if args.inputs == "host" and not dry:
         # The same steps with the episodes in pinned HOST memory (the C ABI takes device pointers; `value` above is the resident
@@ -626,7 +659,7 @@ def run(args):
     fp16_mode = None
     strict_mode = None
     config_legs = None
-    if (not dry and rank == 0 and world == 1 and args.precision == "bf16" and not args.no_fp16_leg
+    if (full and not dry and rank == 0 and world == 1 and args.precision == "bf16" and not args.no_fp16_leg
             and B * frames_per_ep > 160):              # (small steps: a handful of them does not time anything)
         # The 16-bit mode that meets the north-star tolerance on the goldens (precision "fp16": IEEE-half operands everywhere, same kernels), timed
         # in the same process on the same resident steps: `value` stays BASELINE's bf16 configuration, this object says what the
@@ -637,7 +670,7 @@ def run(args):
         if ARCH.startswith("ViT"):
             strict_mode = timed_leg(args.config, "fp16_strict", B, max(4, min(args.steps, 10)), dev, timer, weights=(sd, tt, te), batches=batches,
                                     kernel_events=not args.no_kernel_events)
-    if (not dry and rank == 0 and world == 1 and args.precision == "bf16" and args.config == "cfg2" and not args.no_config_legs
+    if (full and not dry and rank == 0 and world == 1 and args.precision == "bf16" and args.config == "cfg2" and not args.no_config_legs
             and B * frames_per_ep > 160):
         # BASELINE configs[2..3] in front of the driver: 3 timed steps of the harness's batch (12 / 11 episodes), bf16, fp16 and fp16_strict, with golden parity
         config_legs = {}
@@ -686,6 +719,7 @@ def run(args):
             "per_rank_episodes_per_s": {"min": round(args.steps * B / max(rank_elapsed), 3), "max": round(args.steps * B / min(rank_elapsed), 3),
                                         "ranks": len(rank_elapsed)},
             "collective": collective,
+            "full": full,
         }
         if dry:
             out["dry_run"] = True
@@ -695,24 +729,25 @@ def run(args):
         else:
             e2e_tflops = eps_per_s / world * tflop_exec                      # executed FLOPs, not the reference path's
             out["end_to_end_vit_tflops_per_gpu"] = round(e2e_tflops, 2)
-            if main_gemm is not None:
-                ms, flops, n = main_gemm
-                achieved = flops / (ms * 1e-3) / 1e12
-                traffic, traffic_src = measured_traffic(B) if (args.config == "cfg2" and args.precision == "bf16") else (None, None)
-                out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS,
-                                   "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                                   "frac_scope": "dominant kernel only: the bf16 MFMA GEMM launches of rank 0 (HIP events)",
-                                   # episodes/s x TFLOP/episode / peak -- every kernel, launch gaps and the tail included
-                                   "frac_end_to_end": round(e2e_tflops / PEAK_BF16_TFLOPS, 4),
-                                   "traffic": traffic, "traffic_source": traffic_src,                 # the PMC passes were made on cfg2, bf16
-                                   "kernel": GEMM_KERNEL_NOTE,
-                                   "launches": n, "avg_launch_us": round(ms * 1e3 / n, 2),
-                                   "algorithmic_gflop_per_launch": round(flops / n / 1e9, 3),
-                                   "event_sampling": "every step" if event_every == 1 else "every %d-th timed step" % event_every, "gemm_share_of_step": round(ms / (elapsed * 1e3 * len(range(0, args.steps, event_every)) / max(args.steps, 1)), 4)}
-            else:
-                out["roofline"] = None
-            out["parity"] = (golden_parity(first_logits["v"][0], args.precision)
-                             if args.config == "cfg2" and "v" in first_logits else {"checked": False, "reason": "config has no in-bench golden"})
+            if full:
+                if main_gemm is not None:
+                    ms, flops, n = main_gemm
+                    achieved = flops / (ms * 1e-3) / 1e12
+                    traffic, traffic_src = measured_traffic(B) if (args.config == "cfg2" and args.precision == "bf16") else (None, None)
+                    out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS,
+                                       "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+                                       "frac_scope": "dominant kernel only: the bf16 MFMA GEMM launches of rank 0 (HIP events)",
+                                       # episodes/s x TFLOP/episode / peak -- every kernel, launch gaps and the tail included
+                                       "frac_end_to_end": round(e2e_tflops / PEAK_BF16_TFLOPS, 4),
+                                       "traffic": traffic, "traffic_source": traffic_src,                 # the PMC passes were made on cfg2, bf16
+                                       "kernel": GEMM_KERNEL_NOTE,
+                                       "launches": n, "avg_launch_us": round(ms * 1e3 / n, 2),
+                                       "algorithmic_gflop_per_launch": round(flops / n / 1e9, 3),
+                                       "event_sampling": "every step" if event_every == 1 else "every %d-th timed step" % event_every, "gemm_share_of_step": round(ms / (elapsed * 1e3 * len(range(0, args.steps, event_every)) / max(args.steps, 1)), 4)}
+                else:
+                    out["roofline"] = None
+                out["parity"] = (golden_parity(first_logits["v"][0], args.precision)
+                                 if args.config == "cfg2" and "v" in first_logits else {"checked": False, "reason": "config has no in-bench golden"})
             if fp16_mode is not None:
                 fp16_mode["relative_to_value"] = round(fp16_mode["value"] / eps_per_s, 4)
                 out["fp16_mode"] = fp16_mode
@@ -724,7 +759,8 @@ def run(args):
             if host_inputs is not None:
                 host_inputs["resident_episodes_per_s"] = round(eps_per_s / world, 3)
                 out["inputs_host"] = host_inputs
-            out["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()
+            if full:
+                out["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()
     if use_dist:
         dist.destroy_process_group()
     if rank == 0:

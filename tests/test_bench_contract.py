@@ -2,11 +2,12 @@
 
 CPU (`-m "not gpu"`): the self-spawn launcher (`python bench.py --gpus 2` with no launcher environment) rehearsed with
 `--dry-run` -- gloo process group, barrier, the one all-gather, max-over-ranks timing, ONE JSON line from rank 0 -- and the
-same protocol under `torch.distributed.run`.
+same protocol under `torch.distributed.run`; `--dump-outputs` of a dry run.
 
-GPU (`-m gpu`): the real bench line carries `roofline` (+ `frac_end_to_end`), `parity` against the reference-generated
-cfg2 golden in the configuration that was timed, and the RCCL (backend "nccl") all-gather path at world size 1
-(`CFSAR_BENCH_FORCE_DIST=1`); `--gpus 2` self-spawn when the box has two GPUs.
+GPU (`-m gpu`): a plain bench line carries the headline only, and `--dump-outputs` writes what its last timed step computed; the
+`--full` line carries `roofline` (+ `frac_end_to_end`), `parity` against the reference-generated cfg2 golden in the configuration
+that was timed, and the RCCL (backend "nccl") all-gather path at world size 1 (`CFSAR_BENCH_FORCE_DIST=1`); `--gpus 2` self-spawn
+when the box has two GPUs.
 """
 import json
 import os
@@ -104,6 +105,17 @@ def test_single_process_dry_run():
     assert out["n_gpus"] == 1 and out["dry_run"] is True
 
 
+def test_dry_run_dump_outputs_and_steps(tmp_path):
+    """--steps sets the number of timed steps, --dump-outputs writes the last step's per-episode results as float32 .npy."""
+    import numpy as np
+    out = _run([sys.executable, BENCH, "--steps", "5", "--warmup", "2", "--episodes-per-step", "3", "--dry-run", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] >= 0 and out["full"] is False
+    top1 = np.load(str(tmp_path / "top1.npy"))
+    assert top1.dtype == np.float32 and top1.shape == (3,)
+    with pytest.raises(subprocess.CalledProcessError):
+        subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-run"], cwd=ROOT, capture_output=True, check=True, timeout=120)
+
+
 needs_gpu = pytest.mark.skipif(not torch.cuda.is_available(), reason="no GPU")
 
 
@@ -112,8 +124,8 @@ needs_gpu = pytest.mark.skipif(not torch.cuda.is_available(), reason="no GPU")
 def test_bench_line_bf16_parity_roofline_rccl_ws1():
     """The timed configuration (bf16, batched episodes, persistent GEMM kernels) is the one whose logits are compared with
     the reference golden; the RCCL all-gather path runs (world size 1)."""
-    out = _run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--episodes-per-step", "16", "--no-cpu-baseline", "--no-config-legs"],
-               env_extra={"CFSAR_BENCH_FORCE_DIST": "1"})
+    out = _run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--episodes-per-step", "16", "--full", "--no-cpu-baseline",
+                "--no-config-legs"], env_extra={"CFSAR_BENCH_FORCE_DIST": "1"})
     assert out["n_gpus"] == 1 and out["unit"] == "episodes/s" and out["value"] > 0
     par = out["parity"]
     from clip_fsar_amd import LOGITS_TOLERANCE
@@ -138,7 +150,7 @@ def test_bench_line_bf16_parity_roofline_rccl_ws1():
 @pytest.mark.gpu
 @needs_gpu
 def test_bench_line_fp32_meets_north_star_tolerance():
-    out = _run([sys.executable, BENCH, "--steps", "1", "--warmup", "1", "--episodes-per-step", "16", "--precision", "fp32",
+    out = _run([sys.executable, BENCH, "--steps", "1", "--warmup", "1", "--episodes-per-step", "16", "--precision", "fp32", "--full",
                 "--no-cpu-baseline", "--no-kernel-events"])
     par = out["parity"]
     assert par["checked"] and par["argmax_equal"] and par["max_abs_dlogits"] < 1e-3, par     # north-star tolerance
@@ -156,7 +168,7 @@ def test_bench_self_spawn_two_gpus_rccl():
 def test_bench_line_carries_cfg3_cfg4_legs():
     """BASELINE configs[2..3] in front of the driver: the default run's `configs` object holds short cfg3 / cfg4 legs in
     bf16, fp16 and fp16_strict, each with its rate, roofline fractions and golden parity."""
-    out = _run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-fp16-leg"])
+    out = _run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fp16-leg"])
     from clip_fsar_amd import LOGITS_TOLERANCE
     legs = out["configs"]
     assert sorted(legs) == ["cfg3_bf16", "cfg3_fp16", "cfg3_fp16_strict", "cfg4_bf16", "cfg4_fp16", "cfg4_fp16_strict"]
@@ -164,3 +176,23 @@ def test_bench_line_carries_cfg3_cfg4_legs():
         prec = name.split("_", 1)[1]
         assert leg["value"] > 0 and 0 < leg["roofline"]["frac_end_to_end"] <= leg["roofline"]["frac"] + 0.05, leg
         assert leg["parity"]["checked"] and leg["parity"]["argmax_equal"] and leg["parity"]["max_abs_dlogits"] < LOGITS_TOLERANCE[prec], leg
+
+
+@pytest.mark.gpu
+@needs_gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline only; --dump-outputs holds what its last timed step returned.  With one timed step that step is
+    batch 0, whose first episode is the cfg2 golden case: the dumped logits of that episode are inside the bf16 bound of the golden."""
+    import numpy as np
+    from clip_fsar_amd import LOGITS_TOLERANCE
+    B = 16
+    out = _run([sys.executable, BENCH, "--steps", "1", "--warmup", "1", "--episodes-per-step", str(B), "--dump-outputs", str(tmp_path)])
+    assert out["full"] is False and out["steps"] == 1 and out["dtype"] == "bf16" and out["higher_is_better"] is True
+    assert not {"roofline", "parity", "fp16_mode", "strict_mode", "configs", "cpu_baseline"} & set(out), sorted(out)
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - B) < 0.01 * B           # value = B episodes per ms_per_step
+    lg, cl, top1 = (np.load(str(tmp_path / n)) for n in ("logits.npy", "class_logits.npy", "top1.npy"))
+    assert lg.dtype == cl.dtype == top1.dtype == np.float32
+    assert lg.shape == (B, 5, 5) and cl.shape == (B, 10, 64) and top1.shape == (B,)
+    assert abs(float(top1.mean()) - out["top1_acc_mean"]) < 1e-3
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "head_cfg2_B16_5w1s_T8.npz"))["logits"]
+    assert float(np.abs(lg[0] - ref).max()) < LOGITS_TOLERANCE["bf16"]

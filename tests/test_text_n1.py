@@ -1,6 +1,7 @@
 """N1: CLIP text side.  CPU: tokenizer ids == the reference's tokenize() (fixture generated from the real
-reference; needs the third-party BPE merges file, so it is skipped where that file is absent) and the oracle's
-encode_text == the reference's CLIP.encode_text.  GPU: the HIP text encoder == the reference outputs."""
+reference) and the oracle's encode_text == the reference's CLIP.encode_text.  GPU: the HIP text encoder == the reference outputs.
+The third-party BPE merges file is not committed: the tokenizer tests read tests/golden/bpe_merges_subset.txt.gz, the merges these
+texts use at their ranks in the full file (oracle/make_bpe_subset.py), or the full file where CLIP_BPE_PATH names it."""
 import json
 import os
 
@@ -12,10 +13,7 @@ import clip_fsar_amd.text as ctext
 import clipfsar_oracle as orc
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "text_cases.npz")
-# the third-party merges file is never committed; dev runs keep a git-ignored copy under tests/_local/
-_CANDIDATES = [os.environ.get("CLIP_BPE_PATH", ""), "/root/reference/models/base/bpe_simple_vocab_16e6.txt.gz",
-               os.path.join(os.path.dirname(__file__), "_local", "bpe_simple_vocab_16e6.txt.gz")]
-BPE = next((p for p in _CANDIDATES if p and os.path.exists(p)), _CANDIDATES[1])
+BPE = os.environ.get("CLIP_BPE_PATH") or os.path.join(os.path.dirname(__file__), "golden", "bpe_merges_subset.txt.gz")
 
 
 def _gold():
@@ -23,7 +21,6 @@ def _gold():
     return {k: z[k] for k in z.files}
 
 
-@pytest.mark.skipif(not os.path.exists(BPE), reason="CLIP BPE merges file not available")
 def test_tokenizer_matches_reference_ids():
     g = _gold()
     texts = json.loads(str(g["texts"]))
@@ -88,7 +85,6 @@ def test_causal_seq_attention_kernel():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BPE), reason="CLIP BPE merges file not available")
 def test_head_builds_text_tables_from_class_names():
     """The head's init-time path (few_shot.py:2714-2728): class names -> prompts -> tokenizer -> HIP text encoder."""
     if not torch.cuda.is_available():

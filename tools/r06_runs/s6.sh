@@ -7,8 +7,8 @@ export TMPDIR=/tmp
 O=gpurun_out/r06_s6; mkdir -p $O
 timeout 3000 python -m pytest tests -q -m gpu > $O/pytest_all.log 2>&1; echo "rc $?" >> $O/pytest_all.log; tail -4 $O/pytest_all.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -3 $O/smoke.log
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-config-legs"
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-config-legs"
 timeout 600 $B --precision fp16 --no-fp16-leg > $O/bench_fp16.json 2> $O/bench_fp16.err
 timeout 600 $B --precision fp16_strict --no-fp16-leg > $O/bench_strict.json 2> $O/bench_strict.err
 timeout 600 $B --precision fp32 --no-fp16-leg > $O/bench_fp32.json 2> $O/bench_fp32.err
@@ -34,4 +34,4 @@ for prec in fp16 fp16_strict; do
   cd $GRAFT_REPO_ROOT; python tools/trace_summary.py $P/trace/t_kernel_trace.csv 0 > $P/kernel_summary.txt; rm -rf $P/trace; head -8 $P/kernel_summary.txt | cut -c1-150
 done
 cp gpurun_out/prof_r06/gemm_traffic.json profiles/r06_gemm_traffic.json      # (on the box: the line below then quotes the traffic of THIS build)
-timeout 900 python bench.py --steps 20 --no-cpu-baseline > $O/bench_with_traffic.json 2> $O/bench_with_traffic.err; tail -c 200 $O/bench_with_traffic.json
+timeout 900 python bench.py --full --steps 20 --no-cpu-baseline > $O/bench_with_traffic.json 2> $O/bench_with_traffic.err; tail -c 200 $O/bench_with_traffic.json
