@@ -36,6 +36,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES + DEV_ONLY_SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
+# The support gallery (include/clipfsar_gallery.h): a library of its own, built on the product path beside libclipfsar_hip.so, with its own
+# staleness check and its own resource report (build/resource_usage.json stays the product library's).
+GALLERY_SOURCE = "gallery.hip"
+GALLERY_LIB = os.path.join(HERE, "libclipfsar_gallery.so")
+GALLERY_HEADER = os.path.join(os.path.dirname(HERE), "include", "clipfsar_gallery.h")
+GALLERY_USAGE = os.path.join(HERE, "build", "gallery", "resource_usage.json")
 
 
 def _parse_usage(text: str) -> dict:
@@ -62,7 +68,7 @@ def _stale(lib=LIB) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f != GALLERY_SOURCE] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -73,8 +79,46 @@ def _stale(lib=LIB) -> bool:
 PACKED_LIB = os.path.join(HERE, "libclipfsar_hip_packed.so")
 
 
+def _gallery_stale() -> bool:
+    if not os.path.exists(GALLERY_LIB):
+        return True
+    t = os.path.getmtime(GALLERY_LIB)
+    deps = [os.path.join(CSRC, GALLERY_SOURCE), os.path.join(CSRC, "common.h"), GALLERY_HEADER,
+            os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]    # common.h includes the latter
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_gallery(force: bool = False, verbose: bool = True) -> str:
+    """libclipfsar_gallery.so from csrc/gallery.hip: the product FLAGS and the packed-fp32 fence, resource report -> GALLERY_USAGE"""
+    if not force and not _gallery_stale():
+        return GALLERY_LIB
+    bdir = os.path.dirname(GALLERY_USAGE)
+    os.makedirs(bdir, exist_ok=True)
+    obj = os.path.join(bdir, GALLERY_SOURCE.replace(".hip", ".o"))
+    cmd = [HIPCC] + FLAGS + NO_PACKED_FP32 + ["-c", os.path.join(CSRC, GALLERY_SOURCE), "-o", obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if p.returncode != 0:
+        raise RuntimeError("hipcc failed on %s:\n%s" % (GALLERY_SOURCE, p.stdout))
+    rest = "\n".join(l for l in p.stdout.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l)
+    if verbose and rest.strip():
+        print(rest)
+    import json
+    with open(GALLERY_USAGE, "w") as f:
+        json.dump(_parse_usage(p.stdout), f, indent=0, sort_keys=True)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", GALLERY_LIB, obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return GALLERY_LIB
+
+
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
-    """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH)"""
+    """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
+    The product build also builds the gallery library (build_gallery)."""
+    if not (dev or packed or variant):
+        build_gallery(force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT):
         return LIB_OUT

@@ -777,6 +777,25 @@ class HipTemporalHead:
             self._ws_rows = rows
         return self._ws
 
+    def run_layers(self, rows, n_a, len_a, n_b, len_b):
+        """context2's layer loop (few_shot.py:990-999) on the first `rows` rows of the workspace's X (_workspace(rows)["X"], written by the
+        caller): n_a sequences of len_a rows, then n_b of len_b (either count may be 0).  Returns the workspace buffer that holds the
+        output; it is overwritten by the next call."""
+        E = self.dim
+        ws = self._workspace(rows)
+        cur, nxt = ws["X"], ws["z"]
+        for l in self.layers:                                                            # few_shot.py:990-999
+            inner = l["inner"]
+            hd = inner // self.heads
+            hip.layernorm(cur, ws["n"], l["norm"][0], l["norm"][1], rows, E)              # shared LN for q,k,v (:971-977)
+            hip.gemm(ws["n"], l["w_qkv"], ws["qkv"], M=rows)                              # to_q|to_k|to_v, no bias
+            hip.seq_attention(ws["qkv"], ws["o"], n_a, len_a, n_b, len_b, self.heads, hd, hd ** -0.5)
+            hip.gemm(ws["o"], l["w_out"], ws["y"], bias=l["b_out"], residual=cur, M=rows)   # to_out + q residual
+            hip.gemm(ws["y"], l["w1"], ws["u"], bias=l["b1"], act=hip.ACT_GELU_ERF, M=rows)
+            hip.gemm(ws["u"], l["w2"], nxt, bias=l["b2"], residual=ws["y"], M=rows)         # ff(x) + x
+            cur, nxt = nxt, cur
+        return cur
+
     def forward(self, feats, text_test, support_labels, real_support_labels, B, S, Q, T, way, merge_before=False,
                 single_direct=False, taps=None):
         """feats [B, S+Q, T, E] fp32 -> logits [B, Q, way] fp32."""
@@ -785,19 +804,8 @@ class HipTemporalHead:
         rows_q, rows_s = B * Q * T, B * Sp * (T + 1)
         rows = rows_q + rows_s
         ws = self._workspace(rows)
-        X = ws["X"]
-        hip.build_sequences(feats, text_test, support_labels, real_support_labels, X, B, S, Q, T, E, way, merge_before)
-        cur, nxt = X, ws["z"]
-        for l in self.layers:                                                            # few_shot.py:990-999
-            inner = l["inner"]
-            hd = inner // self.heads
-            hip.layernorm(cur, ws["n"], l["norm"][0], l["norm"][1], rows, E)              # shared LN for q,k,v (:971-977)
-            hip.gemm(ws["n"], l["w_qkv"], ws["qkv"], M=rows)                              # to_q|to_k|to_v, no bias
-            hip.seq_attention(ws["qkv"], ws["o"], B * Q, T, B * Sp, T + 1, self.heads, hd, hd ** -0.5)
-            hip.gemm(ws["o"], l["w_out"], ws["y"], bias=l["b_out"], residual=cur, M=rows)   # to_out + q residual
-            hip.gemm(ws["y"], l["w1"], ws["u"], bias=l["b1"], act=hip.ACT_GELU_ERF, M=rows)
-            hip.gemm(ws["u"], l["w2"], nxt, bias=l["b2"], residual=ws["y"], M=rows)         # ff(x) + x
-            cur, nxt = nxt, cur
+        hip.build_sequences(feats, text_test, support_labels, real_support_labels, ws["X"], B, S, Q, T, E, way, merge_before)
+        cur = self.run_layers(rows, B * Q, T, B * Sp, T + 1)
         protos = torch.empty(B, way, T, E, device=self.dev, dtype=torch.float32)
         hip.prototypes(cur[rows_q:], support_labels, protos, B, S, Sp, T, E, way, merge_before)
         logits = torch.empty(B, Q, way, device=self.dev, dtype=torch.float32)
