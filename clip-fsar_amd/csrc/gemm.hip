@@ -999,13 +999,6 @@ __device__ __forceinline__ int tile_group(const GemmArgs& p, int ntiles) {
 #ifdef CFSAR_DEV
 static int g_variant_override = 0, g_dbg_override = 0;   // dev tool: in-process A/B (tools/gemm_ab.py)
 #endif
-// product policy of the gemm_vit.hip kernel (measured, M = 252 160: profiles/r02_gemm_ab.md): the LDS-DMA operand path for the
-// short-K GEMMs (QKV 859 vs 871 us register-staged vs 890 p12; c_fc 1 279 vs 1 335 vs 1 292), the register-staged path (loads two
-// K tiles ahead) for K > 1 024 (c_proj 1 093 vs 1 156 us with DMA), write-through (sc1) stores where the output is not read back
-// by the same launch (QKV 850 vs 859, c_fc 1 273 vs 1 279; the in-place residual update is slower with it: 365 vs 350)
-constexpr bool kUseVitKernel = true;
-constexpr int kVitGroup = 8, kVitColfast = 0;
-
 // ---- helpers shared by the register-staged kernels (p10, p12)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // native vector: loads/stores stay SSA values (no memcpy)
 
@@ -1242,23 +1235,12 @@ static inline int persistent_grid() {
     return n >= 8 ? n : 8;
 }
 
+// p10 runs the implicit-GEMM 3x3 convolution with Cout > 128 (cfsar_conv3x3_nhwc); p12 replaced its plain-GEMM form (see cfsar_gemm_ex)
 template <typename TO, int ACT, bool HAS_RES, bool PERSIST, bool CONV = false, typename TI = __bf16>
 int launch_p10_inst(const GemmArgs& a, hipStream_t s) {
     if (int rc = cfsar_ensure_lds(reinterpret_cast<const void*>(&gemm_kernel_p10<TO, ACT, HAS_RES, PERSIST, CONV, TI>), LDS4, "cfsar_gemm")) return rc;
     hipLaunchKernelGGL((gemm_kernel_p10<TO, ACT, HAS_RES, PERSIST, CONV, TI>), dim3(PERSIST ? persistent_grid() : a.ntiles), dim3(256), LDS4, s, a);
     return cfsar_check_launch("cfsar_gemm(p10)");
-}
-
-template <typename TO, bool PERSIST>
-int launch_p10(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    a.tiles_n = (a.N + BN4 - 1) / BN4;
-    a.ntiles = ((a.M + BM4 - 1) / BM4) * a.tiles_n;
-    const bool r = a.res != nullptr;
-    if (a.row_group > 0 || a.res_mod > 0 || a.act == CFSAR_ACT_GELU_ERF || a.K % 64 != 0) return -2;
-    if ((size_t)a.M * a.lda * 2 >= (1ull << 32) || (size_t)a.N * a.ldw * 2 >= (1ull << 32)) return -2;   // 32-bit offsets
-    if (a.act == CFSAR_ACT_QUICKGELU) return r ? -2 : launch_p10_inst<TO, CFSAR_ACT_QUICKGELU, false, PERSIST>(a, s);
-    return r ? launch_p10_inst<TO, CFSAR_ACT_NONE, true, PERSIST>(a, s) : launch_p10_inst<TO, CFSAR_ACT_NONE, false, PERSIST>(a, s);
 }
 
 // ============================================================================================================
@@ -1749,9 +1731,10 @@ extern "C" int cfsar_gemm_ex(const void* A, const void* W, void* out, const floa
     a.conv_H = a.conv_W = a.conv_lgC = 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // Kernel choice.  Product builds take the measured policy below (`forced` is the constant 0 and its branches fold away); dev
-    // builds (CFSAR_DEV, include/clipfsar_hip_dev.h) can force a variant for in-process A/B: 1 = v1 (128x128, also the fp32 path),
-    // 2 = p3 (256x128, asm LDS-DMA), 10 / 11 = p10 (one wave per SIMD) / persistent, 12 / 13 = p12 (two waves per SIMD) /
-    // persistent, 14 / 15 = skinny fp32 kernel always / never, 20+ = the gemm_vit.hip kernel (see there).
+    // builds (CFSAR_DEV, include/clipfsar_hip_dev.h) can force a variant for in-process A/B, each a kernel the product also runs:
+    // 1 = v1 (128x128, also the fp32 path), 2 = p3 (256x128, asm LDS-DMA), 12 / 13 = p12 (two waves per SIMD) / persistent,
+    // 14 / 15 = skinny fp32 kernel always / never, 20 / 28 = the gemm_vit.hip kernel on any shape with the register-staged / the
+    // early-DMA operand path (20 + 4 x path; store policy and the rest from cfsar_vit_policy).
 #ifdef CFSAR_DEV
     a.dbg = g_dbg_override;
     const int forced = g_variant_override;
@@ -1787,29 +1770,24 @@ extern "C" int cfsar_gemm_ex(const void* A, const void* W, void* out, const floa
         return launch_skinny2_inst<4>(a, s);       // (same-process A/B at 1 360 rows, us: N = 512, K = 512: 26 vs 39; K = 2 048: 80 vs 134; 640 x 512 x 768: 24 vs 54;
                                                    //  N >= 1 536 stays on the fp32-MFMA kernel: 41 vs 73-90; skinny_ab.py (archived probe))
     // The ViT-block GEMMs at batch scale (bias [+ QuickGELU] -> bf16, or bias + fp16 residual -> fp16; >= two 256x256 tiles per
-    // CU): the persistent kernel of gemm_vit.hip whose operand pipeline runs through the epilogues.  Dev builds: variant
-    // 20 + 4 * opath + store forces it on any shape; dbg bit 256 = column-fastest tile walk, bits 9-11 = band group (see below).
+    // CU): the persistent kernel of gemm_vit.hip whose operand pipeline runs through the epilogues.  Dev builds: variants 20 / 28
+    // force it on any shape; dbg bit 256 = column-fastest tile walk, bits 9-11 = band group (see below).
     if (in_dtype == CFSAR_BF16 && row_group == 0 && res_mod == 0 && row_off == 0 &&
-        ((forced == 0 && kUseVitKernel && tiles4 >= 512) || (forced >= 20 && forced < 44))) {
+        ((forced == 0 && tiles4 >= 512) || forced == 20 || forced == 28)) {
         VitGemmCall c;
         c.A = A; c.W = W; c.out = out; c.bias = bias; c.res = residual;
         c.rowstats = nullptr; c.cvec = nullptr; c.stats_out = nullptr;
         c.part = nullptr; c.part_slots = 0; c.part_eps = 0.f;
         c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldw = ldw; c.ldo = ldo; c.ldr = ldr;
         c.in_dtype = in_dtype; c.out_dtype = out_dtype; c.res_dtype = res_dtype; c.act = act; c.relu = relu;
-        c.opath = cfsar_vit_policy_opath(K);
-        c.store = residual ? 0 : 2;
-        c.group = kVitGroup; c.colfast = kVitColfast; c.dbg = 0;
+        c.pol = cfsar_vit_policy(residual ? kVitGemmResidual : kVitGemmPlain, K); c.dbg = 0;
         c.hb_tokens = 0; c.hb_heads = 0; c.ha_tokens = 0;
 #ifdef CFSAR_DEV
-        if (forced >= 20 && forced < 31) { c.opath = (forced - 20) >> 2; c.store = (forced - 20) & 3; }
-        else if (forced >= 40) { c.opath = 5; c.store = forced - 40; }      // 40 / 42: one wave per SIMD, 128 x 128 wave tiles (gemm_vit1w.hip)
-        else if (forced >= 36) { c.opath = 4; c.store = forced - 36; }      // 36 / 38: the two-workgroups-per-CU kernel (gemm_vit4.hip), plain / write-through stores
-        else if (forced >= 31) { c.opath = 2; c.store = forced - 28; }      // 31..34: store-policy A/B on the early-DMA path
+        if (forced != 0) c.pol.opath = (forced - 20) >> 2;
         c.dbg = g_dbg_override;
-        if (g_dbg_override & 256) c.colfast = 1;
+        if (g_dbg_override & 256) c.pol.colfast = 1;
         constexpr int groups[8] = {0, 4, 16, 2, 32, 1, 3, 6};
-        if ((g_dbg_override >> 9) & 7) c.group = groups[(g_dbg_override >> 9) & 7];
+        if ((g_dbg_override >> 9) & 7) c.pol.group = groups[(g_dbg_override >> 9) & 7];
 #endif
         const int rc = cfsar_gemm_vit_try(c, s);
         if (rc != -2) return rc;
@@ -1835,11 +1813,6 @@ extern "C" int cfsar_gemm_ex(const void* A, const void* W, void* out, const floa
             if (rc != -2) return rc;
         }
         return launch<__bf16, _Float16>(a, s);
-    }
-    if (in_dtype == CFSAR_BF16 && (forced == 10 || forced == 11)) {      // 11 = p10 persistent (one workgroup per CU)
-        const int rc = forced == 10 ? (out_dtype == CFSAR_BF16 ? launch_p10<__bf16, false>(a, s) : launch_p10<float, false>(a, s))
-                                    : (out_dtype == CFSAR_BF16 ? launch_p10<__bf16, true>(a, s) : launch_p10<float, true>(a, s));
-        if (rc != -2) return rc;
     }
     const bool use_p3 = (forced != 0 && forced != 1) || (forced == 0 && in_dtype == CFSAR_BF16 && M >= 1024);
     if (use_p3) {

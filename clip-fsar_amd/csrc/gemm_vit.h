@@ -55,6 +55,22 @@ struct VitGemmArgs {          // kernel argument block
 #endif
 };
 
+// The launch policy of the persistent kernel, one rule for every caller (same-box A/B records: the comment at its definition).
+enum VitLaunchKind {
+    kVitLnfold,           // cfsar_gemm_lnfold* (QKV, c_fc)
+    kVitResidual,         // cfsar_gemm_residual_stats* (out_proj, c_proj)
+    kVitWide,             // cfsar_gemm_residual_wide (the fp16 numerics mode's residual launches)
+    kVitGemmPlain,        // cfsar_gemm_ex: bias [+ activation] -> bf16
+    kVitGemmResidual,     // cfsar_gemm_ex: bias + bf16 / fp16 residual
+};
+struct VitPolicy {
+    int opath;            // operand path: 0 register-staged, 2 LDS-DMA issued one barrier early (1, LDS-DMA, serves K = 128 whatever is asked)
+    int store;            // store policy of the output: 0 write-back, 2 write-through + nt
+    int group, colfast;   // tile walk inside an XCD's range (tile_of)
+};
+// K: the K of one operand word (split-weight launches walk 2 K or 3 K and keep the policy of K: profiles/r06_split_policy.txt)
+VitPolicy cfsar_vit_policy(VitLaunchKind kind, int K);
+
 struct VitGemmCall {          // host-side request
     const void* A;
     const void* W;
@@ -69,8 +85,7 @@ struct VitGemmCall {          // host-side request
     float part_eps;
     int M, N, K, lda, ldw, ldo, ldr;
     int in_dtype, out_dtype, res_dtype, act, relu;      // in_dtype: A / W (bf16, or fp16 in the fp16 numerics mode and LN-folded)
-    int opath, store;         // operand path (0 register-staged, 1 LDS-DMA), store policy (0 default, 1 nt, 2 sc1; dev builds)
-    int group, colfast;
+    VitPolicy pol;            // cfsar_vit_policy
     int dbg;
     int hb_tokens, hb_heads, ha_tokens;
     int ka = 0;               // K of A when the weights are split ([N, 2 ka]); 0 = K
@@ -85,10 +100,3 @@ struct VitGemmCall {          // host-side request
 
 // 0 = launched, > 0 = error (cfsar_last_error), -2 = outside this kernel's contract (caller falls back)
 int cfsar_gemm_vit_try(const VitGemmCall& c, hipStream_t s);
-// operand path the policy gives a launch with this K (0 register-staged, 1 LDS-DMA, 2 LDS-DMA issued one barrier earlier, 4 = the
-// two-workgroups-per-CU kernel of gemm_vit4.hip)
-int cfsar_vit_policy_opath(int K);
-// gemm_vit4.hip: the launch `a` (as cfsar_gemm_vit_try filled it) on 192 x 128 tiles, two 4-wave workgroups per CU; -2 = not covered
-int cfsar_gemm_vit4_launch(const VitGemmArgs& a, int mode, bool f16io, int store, hipStream_t s);
-// gemm_vit1w.hip: the same launch with one wave per SIMD (4 waves, 128 x 128 wave tiles, 256 x 256 tiles); opath 5; -2 = not covered
-int cfsar_gemm_vit1w_launch(const VitGemmArgs& a, int mode, bool f16io, int store, hipStream_t s);

@@ -31,15 +31,11 @@
 
 #include "gemm_vit_epi.h"
 
-#ifdef CFSAR_DEV
-int g_cfsar_walk_enable = 0, g_cfsar_walk_phase = 0;      // experiment (dbg bit 25 of cfsar_debug_set_vit_dbg): see attention.hip too
-#endif
-
 namespace {
 
 // OPATH 0: register-staged operands (global_load_dwordx4 -> VGPR -> ds_write_b128), loads two K tiles ahead.
-// OPATH 1: LDS-DMA operands (global_load_lds_dwordx4), one K tile ahead.
-// MODE 0: out = act(A W^T + bias)                      (TI = bf16 operands; dev builds also instantiate TI = f16 for timing A/B)
+// OPATH 1: LDS-DMA operands (global_load_lds_dwordx4), one K tile ahead (built for K = 128 only: SHORTK).
+// MODE 0: out = act(A W^T + bias)                      (TI = bf16 operands)
 // MODE 1: x   = x + A W^T + bias, fp16 in place        (TI = bf16; optional row-statistics partials, see epilogue_rows)
 // MODE 2: out = act(LayerNorm(x) W^T + bias) computed WITHOUT materialising LayerNorm(x) (few_shot.py:605-611, 626-640):
 //         with W' = W diag(gamma) (fp16, folded at init), c_n = sum_k W'_nk, d_n = sum_k beta_k W_nk + bias_n and the row's
@@ -77,14 +73,6 @@ __global__ __launch_bounds__(512, 2) void vit_gemm_kernel(VitGemmArgs p) {
         const int lin = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (b >> 3);
         int tm, tn;
         tile_of(lin, tiles_m, p.tiles_n, p.group, p.colfast, tm, tn);
-#ifdef CFSAR_DEV
-        if (p.dbg & (1 << 26)) {                           // experiment: row bands INTERLEAVED over the XCDs (band = 8 * (i / tiles_n) + xcd: the chip works on one
-            const int i = b >> 3;                          // contiguous front of ~85 bands instead of 8 distant ranges); needs tiles_m % 8 == 0
-            tm = (i / p.tiles_n) * 8 + (b & 7);
-            tn = i - (i / p.tiles_n) * p.tiles_n;
-        }
-        if (p.dbg & (1 << 24)) tm = tiles_m - 1 - tm;      // experiment: row bands walked from the end (the producer's most recent rows first: Infinity Cache)
-#endif
         m0 = tm * TMv;
         n0 = tn * TN;
 #ifdef CFSAR_DEV
@@ -521,9 +509,10 @@ __global__ __launch_bounds__(512, 2) void vit_gemm_kernel(VitGemmArgs p) {
         // accumulator sets through phi copies).  After the last output tile of this workgroup the "next" origin is the current
         // one, so the surplus loads re-read valid memory and the surplus LDS writes land in the free stage.
         u32x4 rv0[4] = {};
-        // (LDS-DMA instance only: in the register-staged one 16 more live registers across the last K step cost 22-30 spills and 10 %)
+        // (LDS-DMA instances only; neutral on the early-DMA path, round 3.  In the register-staged one 16 more live registers across the last
+        // K step cost 22-30 spills and 10 %)
         auto residual_prefetch = [&]() __attribute__((always_inline)) {     // rows rr + 8 it of the wave's first 32-row pass
-            if constexpr (HAS_RES && !WIDE && (OPATH >= kPreMinOpath && OPATH <= kPreMaxOpath)) {
+            if constexpr (HAS_RES && !WIDE && OPATH >= 1) {
                 const int mb_ = m0 + wm * WR, nb_ = n0 + wn * 64;
                 const int ncl_ = nb_ + 64 <= p.N ? nb_ : p.N - 64;
                 const int rr_ = lane >> 3, Q_ = lane & 7;
@@ -583,8 +572,8 @@ __global__ __launch_bounds__(512, 2) void vit_gemm_kernel(VitGemmArgs p) {
                 if (mb + WR <= p.M && nb + 64 <= p.N) epilogue_rows_wide<STORE, true, MIW>(acc, p, mb, nb, lane, slab);
                 else epilogue_rows_wide<STORE, false, MIW>(acc, p, mb, nb, lane, slab);
             } else
-            if (mb + WR <= p.M && nb + 64 <= p.N) epilogue_rows<TO, ACT, HAS_RES, STORE, true, LNFOLD, HAS_RES && (OPATH >= kPreMinOpath && OPATH <= kPreMaxOpath), HB, MIW>(acc, p, mb, nb, lane, slab, rscale, rv0);
-            else epilogue_rows<TO, ACT, HAS_RES, STORE, false, LNFOLD, HAS_RES && (OPATH >= kPreMinOpath && OPATH <= kPreMaxOpath), HB, MIW>(acc, p, mb, nb, lane, slab, rscale, rv0);
+            if (mb + WR <= p.M && nb + 64 <= p.N) epilogue_rows<TO, ACT, HAS_RES, STORE, true, LNFOLD, HAS_RES && OPATH >= 1, HB, MIW>(acc, p, mb, nb, lane, slab, rscale, rv0);
+            else epilogue_rows<TO, ACT, HAS_RES, STORE, false, LNFOLD, HAS_RES && OPATH >= 1, HB, MIW>(acc, p, mb, nb, lane, slab, rscale, rv0);
         }
         CFSAR_TRACE(2);
 #ifdef CFSAR_DEV
@@ -606,15 +595,13 @@ int persistent_grid() {
     return n >= 8 ? n : 8;
 }
 
-// the 192-row form exists for the product policy's instances only (compile time): LN-folded on the early-DMA path with write-through
-// stores, residual on the early-DMA and the register-staged path with plain stores
-constexpr bool vit_has_192(int mode, int opath, int store) {
-    return ((mode == 1 || mode == 6) && store == 0 && (opath == 0 || opath == 2)) || ((mode == 2 || mode == 4) && opath == 2 && store == 2);
+// the 192-row form exists where the product policy launches it (compile time): residual on either operand path, LN-folded on the early-DMA path
+constexpr bool vit_has_192(int mode, int opath) {
+    return mode == 1 || mode == 6 || ((mode == 2 || mode == 4) && opath == 2);
 }
 
-int persistent_grid();
-int vit_pick_miw(int M, int tiles_n, int mode, int opath, int store, int K, int dbg) {
-    if (K == 128 || !vit_has_192(mode, opath, store)) return 4;
+int vit_pick_miw(int M, int tiles_n, int mode, int opath, int K, int dbg) {
+    if (K == 128 || !vit_has_192(mode, opath)) return 4;
     const long long G = persistent_grid();
     const long long t256 = (long long)((M + 255) / 256) * tiles_n, t192 = (long long)((M + 191) / 192) * tiles_n;
     const long long r256 = ((t256 + G - 1) / G) * 256, r192 = ((t192 + G - 1) / G) * 192;
@@ -639,38 +626,42 @@ int launch_inst2(const VitGemmArgs& a, hipStream_t s) {
 template <typename TI, typename TO, int ACT, int MODE, int OPATH, int STORE>
 int launch_inst(const VitGemmArgs& a, hipStream_t s) {
     if (a.K == 128) return launch_inst2<TI, TO, ACT, MODE, 1, STORE, true>(a, s);       // two K tiles: its own instance
-    if constexpr (vit_has_192(MODE, OPATH, STORE)) {
+    if constexpr (vit_has_192(MODE, OPATH)) {
         if (a.miw == 3) return launch_inst2<TI, TO, ACT, MODE, OPATH, STORE, false, 3>(a, s);
     }
     return launch_inst2<TI, TO, ACT, MODE, OPATH, STORE, false>(a, s);
 }
 
-// mode: 0 bias -> bf16, 1 residual -> fp16 in place, 2 LN-folded (fp16 operands) -> bf16; f16io (the fp16 numerics mode): fp16
-// operands in mode 1, fp16 output in mode 2
+// mode: 0 bias -> bf16, 1 residual -> fp16 in place, 2 LN-folded (fp16 operands) -> bf16, 5 bf16 residual, 6 wide residual; f16io (the fp16
+// numerics mode): fp16 operands in mode 1, fp16 output in mode 2.  Only the store policy cfsar_vit_policy gives a mode is instantiated for it:
+// write-back (0) for the residual modes, write-through (2) for the others.
 template <int OPATH, int STORE>
 int launch_path(const VitGemmArgs& a, int mode, bool f16io, hipStream_t s) {
-    if (mode == 5) return launch_inst<__bf16, __bf16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);     // bf16 residual (+ ReLU): RN50 conv3
-    if (mode == 6) return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 6, OPATH, STORE>(a, s);  // wide residual (fp16 numerics mode)
-    if (mode == 1) {
-        if (f16io) return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);
-        return launch_inst<__bf16, _Float16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);
-    }
-    if (mode == 2) {
-        if (f16io) {
-            if (a.hb_tokens > 0) return -2;
-            if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<_Float16, _Float16, CFSAR_ACT_QUICKGELU, 2, OPATH, STORE>(a, s);
-            return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 2, OPATH, STORE>(a, s);
+    if constexpr (STORE == 0) {
+        if (mode == 5) return launch_inst<__bf16, __bf16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);     // bf16 residual (+ ReLU): RN50 conv3
+        if (mode == 6) return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 6, OPATH, STORE>(a, s);  // wide residual (fp16 numerics mode)
+        if (mode == 1) {
+            if (f16io) return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);
+            return launch_inst<__bf16, _Float16, CFSAR_ACT_NONE, 1, OPATH, STORE>(a, s);
         }
-        if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<_Float16, __bf16, CFSAR_ACT_QUICKGELU, 2, OPATH, STORE>(a, s);
-        if (a.hb_tokens > 0) return launch_inst<_Float16, __bf16, CFSAR_ACT_NONE, 4, OPATH, STORE>(a, s);
-        return launch_inst<_Float16, __bf16, CFSAR_ACT_NONE, 2, OPATH, STORE>(a, s);
+    } else {
+        if (mode == 2) {
+            if (f16io) {
+                if (a.hb_tokens > 0) return -2;
+                if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<_Float16, _Float16, CFSAR_ACT_QUICKGELU, 2, OPATH, STORE>(a, s);
+                return launch_inst<_Float16, _Float16, CFSAR_ACT_NONE, 2, OPATH, STORE>(a, s);
+            }
+            if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<_Float16, __bf16, CFSAR_ACT_QUICKGELU, 2, OPATH, STORE>(a, s);
+            if (a.hb_tokens > 0) return launch_inst<_Float16, __bf16, CFSAR_ACT_NONE, 4, OPATH, STORE>(a, s);
+            return launch_inst<_Float16, __bf16, CFSAR_ACT_NONE, 2, OPATH, STORE>(a, s);
+        }
+        if (mode == 0) {
+            if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<__bf16, __bf16, CFSAR_ACT_QUICKGELU, 0, OPATH, STORE>(a, s);
+            if (a.relu) return launch_inst<__bf16, __bf16, kActRelu, 0, OPATH, STORE>(a, s);
+            return launch_inst<__bf16, __bf16, CFSAR_ACT_NONE, 0, OPATH, STORE>(a, s);
+        }
     }
-#ifdef CFSAR_DEV
-    if (mode == 3) return launch_inst<_Float16, __bf16, CFSAR_ACT_NONE, 0, OPATH, STORE>(a, s);   // timing A/B: fp16 MFMA on a plain GEMM
-#endif
-    if (a.act == CFSAR_ACT_QUICKGELU) return launch_inst<__bf16, __bf16, CFSAR_ACT_QUICKGELU, 0, OPATH, STORE>(a, s);
-    if (a.relu) return launch_inst<__bf16, __bf16, kActRelu, 0, OPATH, STORE>(a, s);
-    return launch_inst<__bf16, __bf16, CFSAR_ACT_NONE, 0, OPATH, STORE>(a, s);
+    return cfsar_fail("cfsar_gemm (vit): internal: no instance of mode %d with store policy %d", mode, STORE);
 }
 
 }  // namespace
@@ -725,7 +716,7 @@ int cfsar_gemm_vit_try(const VitGemmCall& c, hipStream_t s) {
     if (c.corr && !(c.corr_tokens >= 128 && c.in_dtype == CFSAR_F16 && c.out_dtype == CFSAR_F16 && (lnfold || c.wide) && c.hb_tokens == 0))
         return cfsar_fail("cfsar_gemm (vit): the per-frame correction needs >= 128 tokens per frame and an fp16-mode instance (tokens=%d)", c.corr_tokens);
     a.part = c.part; a.part_slots = c.part_slots; a.part_invD = 1.0f / (float)ka; a.part_eps = c.part_eps;
-    if (c.part && !(c.opath == 2 && ka >= 512 && (c.part_slots == 12 || c.part_slots == 16) && c.part_slots * 64 == ka))
+    if (c.part && !(c.pol.opath == 2 && ka >= 512 && (c.part_slots == 12 || c.part_slots == 16) && c.part_slots * 64 == ka))
         return cfsar_fail("cfsar_gemm_lnfold_partials: needs K = 64 slots in {768, 1024} (K=%d, slots=%d)", ka, c.part_slots);
     a.cvec = c.cvec;
     a.stats_out = c.stats_out;
@@ -737,12 +728,12 @@ int cfsar_gemm_vit_try(const VitGemmCall& c, hipStream_t s) {
     a.tiles_n = (c.N + TN - 1) / TN;
     // Tile height: 192 rows when that saves a tenth of the rounds-x-rows the persistent grid walks (one or two episodes per call:
     // 62 bands x 9 columns of 256-row tiles are 2.2 rounds on 256 CUs and cost 3; 83 x 9 of 192 rows cost 3 x 0.75)
-    a.miw = vit_pick_miw(c.M, a.tiles_n, lnfold ? 2 : ((f16res || bf16res) ? (c.wide ? 6 : 1) : 0), c.opath, c.store, c.K, c.dbg);
+    a.miw = vit_pick_miw(c.M, a.tiles_n, lnfold ? 2 : ((f16res || bf16res) ? (c.wide ? 6 : 1) : 0), c.pol.opath, c.K, c.dbg);
     if (c.part && a.miw != 3) return cfsar_fail("cfsar_gemm_lnfold_partials: internal: fused statistics need the 192-row instance");
     if (c.out_miw) *c.out_miw = a.miw;
     a.ntiles = ((c.M + 64 * a.miw - 1) / (64 * a.miw)) * a.tiles_n;
-    a.group = c.group > 0 ? c.group : 8;
-    a.colfast = c.colfast;
+    a.group = c.pol.group;
+    a.colfast = c.pol.colfast;
     a.hb_tokens = c.hb_tokens; a.hb_heads = c.hb_heads; a.ha_tokens = c.ha_tokens;
     if (a.hb_tokens > 0 && !(lnfold && c.act == CFSAR_ACT_NONE && a.hb_tokens >= 128 && a.hb_heads > 0 && c.N == 3 * 64 * a.hb_heads &&
                              c.M % a.hb_tokens == 0))
@@ -751,92 +742,59 @@ int cfsar_gemm_vit_try(const VitGemmCall& c, hipStream_t s) {
         return cfsar_fail("cfsar_gemm_residual_stats: head-blocked A needs M a multiple of tokens");
 #ifdef CFSAR_DEV
     a.dbg = c.dbg;
-    if (g_cfsar_walk_enable) a.dbg |= ((g_cfsar_walk_phase++ & 1) << 24);      // experiment: alternate the walk direction launch by launch
     a.stagger_unit = g_stagger_unit;
     a.trace = g_trace;
 #endif
-    int mode = lnfold ? 2 : (f16res ? (c.wide ? 6 : 1) : (bf16res ? 5 : 0));
-#ifdef CFSAR_DEV
-    if (mode == 0 && c.act == CFSAR_ACT_NONE && (c.dbg & 64)) mode = 3;
-#endif
-    int opath = c.opath;
-#ifdef CFSAR_DEV
-    // Developer library only: the two alternative forms measured in round 5 (profiles/r05_gemm_forms.md; both lose against this kernel).
-    // Calls they do not cover fall back to the 8-wave kernel.
-    if (opath == 4 || opath == 5) {                 // 4 = two 4-wave workgroups per CU (gemm_vit4.hip), 5 = one wave per SIMD (gemm_vit1w.hip)
-        const int rc = opath == 4 ? cfsar_gemm_vit4_launch(a, mode, f16io, c.store, s) : cfsar_gemm_vit1w_launch(a, mode, f16io, c.store, s);
-        if (rc != -2) {
-            if (c.out_miw) *c.out_miw = opath == 4 ? 3 : 4;
-            return rc;
-        }
-        opath = c.K <= 1024 ? 2 : 0;
-    }
-#endif
-    switch (opath * 4 + c.store) {
+    const int mode = lnfold ? 2 : (f16res ? (c.wide ? 6 : 1) : (bf16res ? 5 : 0));
+    // (OPATH 1 is reached through K = 128 alone: launch_inst)
+    switch (c.pol.opath * 4 + c.pol.store) {
         case 0: return launch_path<0, 0>(a, mode, f16io, s);
         case 2: return launch_path<0, 2>(a, mode, f16io, s);
-        case 4: return launch_path<1, 0>(a, mode, f16io, s);
-        case 6: return launch_path<1, 2>(a, mode, f16io, s);
         case 8: return launch_path<2, 0>(a, mode, f16io, s);
         case 10: return launch_path<2, 2>(a, mode, f16io, s);
-#ifdef CFSAR_DEV
-        case 1: return launch_path<0, 1>(a, mode, f16io, s);
-        case 5: return launch_path<1, 1>(a, mode, f16io, s);
-        case 11: return launch_path<2, 3>(a, mode, f16io, s);     // store-policy A/B on the early-DMA path: variants 31 (sc1 nt),
-        case 12: return launch_path<2, 4>(a, mode, f16io, s);     // 32 (sc0 sc1), 33 (sc0 sc1 nt), 34 (sc0)
-        case 13: return launch_path<2, 5>(a, mode, f16io, s);
-        case 14: return launch_path<2, 6>(a, mode, f16io, s);
-#endif
-        default: return -2;
+        default: return cfsar_fail("cfsar_gemm (vit): operand path %d / store policy %d is not built", c.pol.opath, c.pol.store);
     }
 }
 
-namespace {
 #ifdef CFSAR_DEV
-int g_force_opath = -1, g_force_store = -1, g_force_dbg = 0;
+static int g_force_opath = -1, g_force_dbg = 0;
 #endif
-// Operand path (same-box A/B, profiles/r03_gemm_anatomy.md and round 5 below): the LN-folded short-K launches -- QKV, c_fc -- take the LDS-DMA
-// path with the pieces issued right behind the previous step's barrier (2); the residual launches of the one-word stream (out_proj, c_proj) and the
-// long-K c_proj of the two-word stream the register-staged path (0).
-// kind: 0 = LN-folded launch, 1 = residual launch, 2 = wide residual launch of the fp16 mode (developer builds: ablation bits 21 / 22 keep the product policy for the LN-folded / the residual
-// launches, so a forced form can be A/B'd on one kind of launch alone)
-int vit_policy_opath(int K, int kind = -1) {
+// Operand path (same-box A/B, profiles/r02_gemm_ab.md, r03_gemm_anatomy.md): K <= 1 024 (QKV, c_fc, out_proj) the LDS-DMA path with the pieces
+// issued right behind the previous step's barrier (2), longer K (c_proj) the register-staged path (0).  (Round 5 measured the register-staged path on
+// the short-K launches again: out_proj +0.3 %, the bf16 mode's QKV / c_fc +0.35 ... +0.66 % in the bench legs of the DEVELOPER library -- and
+// +0.1 % / -1.3 % with the PRODUCT library, previous build against new build in separate processes: the two builds allocate registers differently
+// (product: 21 spilled registers in the register-staged LN-folded instance, 0 in the LDS-DMA one; developer: 8 and 0; the developer DMA residual
+// instance spills 4 where the product's spills none).  The rule by K stays; an operand-path A/B is only valid between product builds.
+// profiles/r05_lnfold_path_ab.log, r05_outproj_path_ab.log, r05_bench_outproj_path_ab.txt, r05_bench_lnfold_path_ab.txt)
+// Store policy (profiles/r02_gemm_ab.md): write-through + nt where the launch does not read its output back (QKV 850 vs 859 us, c_fc 1 273 vs
+// 1 279), write-back for the in-place residual updates (365 us with write-through vs 350).
+// Tile walk inside an XCD's range (tile_of): the long-K residual launch (c_proj: three or four column tiles per row band, a weight matrix larger
+// than the L2) takes its tiles column-fastest in groups of 16 bands -- 2.4-3 % faster than band-fastest groups of 8 (same-box A/B at 16 and 36
+// episodes, profiles/r05_forms_s31_colfast.log; out_proj, QKV and c_fc lose 1-3 % with it).  The short-K launches (QKV, c_fc, out_proj) walk
+// band-fastest in groups of SIX bands: against groups of 8, c_fc -1.6 ... -2.2 %, out_proj 0 ... -2.4 %, QKV 0 ... -0.9 % at 16 / 36 episodes,
+// ViT-L/14 shapes 0 ... -1 % (groups of 2 / 3 / 4 / 16 / 32 are worse somewhere; profiles/r05_forms_s33_groups.log).  The cfsar_gemm_ex route
+// keeps band-fastest groups of 8.  The walk changes which workgroup computes a tile, never a value.
+VitPolicy cfsar_vit_policy(VitLaunchKind kind, int K) {
+    const bool longk = K > 1024;
+    const bool gemm = kind == kVitGemmPlain || kind == kVitGemmResidual;
+    VitPolicy pol;
+    pol.opath = longk ? 0 : 2;
+    pol.store = (kind == kVitLnfold || kind == kVitGemmPlain) ? 2 : 0;
+    pol.group = gemm ? 8 : (longk ? 16 : 6);
+    pol.colfast = !gemm && longk;
 #ifdef CFSAR_DEV
-    const bool keep = (kind == 0 && (g_force_dbg & (1 << 21))) || ((kind == 1 || kind == 2) && (g_force_dbg & (1 << 22)));
-    if (keep) { }
-    else if (g_force_opath >= 10) { if (K <= 1024) return g_force_opath - 10; }     // 10 + path: short-K launches only
-    else if (g_force_opath >= 0) return g_force_opath;
+    // cfsar_debug_set_vit_paths (10 + path: K <= 1 024 only); ablation bits 21 / 22 keep the policy for the LN-folded / the residual launches, so a
+    // forced path can be A/B'd on one kind of launch alone
+    const bool keep = (kind == kVitLnfold && (g_force_dbg & (1 << 21))) || ((kind == kVitResidual || kind == kVitWide) && (g_force_dbg & (1 << 22)));
+    if (!keep && g_force_opath >= 0 && (g_force_opath < 10 || !longk)) pol.opath = g_force_opath % 10;
 #endif
-    // (Round 5 measured the register-staged path on the short-K launches again: out_proj +0.3 %, the bf16 mode's QKV / c_fc +0.35 ... +0.66 % in the
-    // bench legs of the DEVELOPER library -- and +0.1 % / -1.3 % with the PRODUCT library, previous build against new build in separate processes:
-    // the two builds allocate registers differently (product: 21 spilled registers in the register-staged LN-folded instance, 0 in the LDS-DMA one;
-    // developer: 8 and 0; the developer DMA residual instance spills 4 where the product's spills none).  The rule by K stays; an operand-path A/B is
-    // only valid between product builds.  profiles/r05_lnfold_path_ab.log, r05_outproj_path_ab.log, r05_bench_outproj_path_ab.txt, r05_bench_lnfold_path_ab.txt)
-    (void)kind;
-    return K <= 1024 ? 2 : 0;
+    return pol;
 }
-// Tile walk of the residual launches inside an XCD's range (tile_of): the long-K one (c_proj: three or four column tiles per row band, a weight matrix
-// larger than the L2) takes its tiles column-fastest in groups of 16 bands -- 2.4-3 % faster than the band-fastest groups of 8 that the short-K
-// launches keep (same-box A/B at 16 and 36 episodes, profiles/r05_forms_s31_colfast.log; out_proj, QKV and c_fc lose 1-3 % with it).  The short-K
-// launches (QKV, c_fc, out_proj) walk band-fastest in groups of SIX bands: against groups of 8, c_fc -1.6 ... -2.2 %, out_proj 0 ... -2.4 %, QKV
-// 0 ... -0.9 % at 16 / 36 episodes, ViT-L/14 shapes 0 ... -1 % (groups of 2 / 3 / 4 / 16 / 32 are worse somewhere; profiles/r05_forms_s33_groups.log).
-// The walk changes which workgroup computes a tile, never a value.
-int vit_policy_colfast(int K) { return K > 1024 ? 1 : 0; }
-int vit_policy_group(int K) { return K > 1024 ? 16 : 6; }
-int vit_policy_store(int dflt) {
-#ifdef CFSAR_DEV
-    // (dflt names the kind of launch: 2 = LN-folded, 0 = residual; ablation bits 21 / 22 keep the product policy for that kind)
-    if (g_force_store >= 0 && !((dflt == 2 && (g_force_dbg & (1 << 21))) || (dflt == 0 && (g_force_dbg & (1 << 22))))) return g_force_store;
-#endif
-    return dflt;
-}
-}
-int cfsar_vit_policy_opath(int K) { return vit_policy_opath(K); }      // the cfsar_gemm dispatcher (gemm.hip) uses the same policy
 #ifdef CFSAR_DEV
 #include "../../include/clipfsar_hip_dev.h"
-// dev builds only: operand path / store policy of cfsar_gemm_lnfold and cfsar_gemm_residual_stats; -1 = product policy
-extern "C" void cfsar_debug_set_vit_paths(int opath, int store) { g_force_opath = opath; g_force_store = store; }
-extern "C" void cfsar_debug_set_vit_dbg(int dbg) { g_force_dbg = dbg & ~(1 << 25); g_cfsar_walk_enable = (dbg >> 25) & 1; g_cfsar_walk_phase = 0; }
+// dev builds only: operand path (0 or 2) of every ViT GEMM launch; -1 = product policy
+extern "C" void cfsar_debug_set_vit_paths(int opath) { g_force_opath = opath; }
+extern "C" void cfsar_debug_set_vit_dbg(int dbg) { g_force_dbg = dbg; }
 // trace buffer ([grid][64][4] long long, device memory; NULL = off) and stagger unit (x 64 cycles) for dbg bit 128
 extern "C" void cfsar_debug_set_vit_trace(void* trace, int stagger_unit) { g_trace = static_cast<long long*>(trace); g_stagger_unit = stagger_unit; }
 #endif
@@ -881,15 +839,10 @@ static int gemm_lnfold_impl(const void* x, const void* Wg, void* out, const floa
     c.part = partial; c.part_slots = slots; c.part_eps = eps;
     c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldw = ldw; c.ldo = ldo; c.ldr = 0;
     c.out_dtype = out_dtype; c.in_dtype = CFSAR_F16; c.res_dtype = CFSAR_F32; c.act = act; c.relu = 0;
-    // The policies go by the OPERAND's K: a split-weight launch of K = 768 walks 1 536 but keeps the short-K launches' LDS-DMA path (no spilled registers;
+    // The policy goes by the OPERAND's K: a split-weight launch of K = 768 walks 1 536 but keeps the short-K launches' LDS-DMA path (no spilled registers;
     // the register-staged LN-folded instances spill 29-35) and band-fastest walk.  Product-build A/B in separate processes, round 6 (profiles/r06_split_policy.txt):
-    // strict mode with split QKV 234.8 -> 239.1 episodes/s, split QKV + c_fc 202.6 -> 210.5, split all 191.5 -> 198.1.  -DCFSAR_SPLIT_POLICY_BY_WALK: by the walked K.
-#ifdef CFSAR_SPLIT_POLICY_BY_WALK
-    const int Kp = K;
-#else
-    const int Kp = ka_;
-#endif
-    c.opath = vit_policy_opath(Kp, 0); c.store = vit_policy_store(2); c.group = vit_policy_group(Kp); c.colfast = vit_policy_colfast(Kp); c.dbg = 0;
+    // strict mode with split QKV 234.8 -> 239.1 episodes/s, split QKV + c_fc 202.6 -> 210.5, split all 191.5 -> 198.1.
+    c.pol = cfsar_vit_policy(kVitLnfold, ka_); c.dbg = 0;
     c.hb_tokens = hb_tokens; c.hb_heads = hb_heads; c.ha_tokens = 0;
 #ifdef CFSAR_DEV
     c.dbg = g_force_dbg;
@@ -935,10 +888,10 @@ static int lnfold_partials_impl(const void* x, const void* Wg, void* out, const 
     dbg = g_force_dbg;
 #endif
     // The 192-row instances (small M: one or two episodes per call) finalize the statistics themselves; at batch scale the 256-row
-    // instances have no registers to spare for it and the finalize launch is 0.4 % of the step: two launches from here.
-    const int Kt = wsplit ? 2 * K : K;
-    const bool fused = vit_policy_opath(Kt, 0) == 2 && (slots == 12 || slots == 16) && K >= 512 &&
-                       vit_pick_miw(M, (N + TN - 1) / TN, 2, 2, vit_policy_store(2), Kt, dbg) == 3;
+    // instances have no registers to spare for it and the finalize launch is 0.4 % of the step: two launches from here.  Split-weight
+    // launches keep the two-launch form on purpose (fusing their statistics would change what they launch: a change of its own).
+    const int opath = cfsar_vit_policy(kVitLnfold, K).opath;
+    const bool fused = !wsplit && opath == 2 && (slots == 12 || slots == 16) && vit_pick_miw(M, (N + TN - 1) / TN, 2, opath, K, dbg) == 3;
     if (!fused) {
         if (int rc = cfsar_ln_stats_finalize(partial, rowstats_ws, M, slots, K, eps, stream)) return rc;
         if (tokens > 0) return cfsar_gemm_lnfold_heads(x, Wg, out, cvec, dvec, rowstats_ws, M, N, K, lda, ldw, tokens, heads, stream);
@@ -993,7 +946,7 @@ static int gemm_residual_stats_impl(const void* A, const void* W, void* x, const
     c.part = nullptr; c.part_slots = 0; c.part_eps = 0.f;
     c.M = M; c.N = N; c.K = K; c.lda = lda; c.ldw = ldw; c.ldo = ldx; c.ldr = ldx;
     c.out_dtype = CFSAR_F16; c.in_dtype = in_dtype; c.res_dtype = CFSAR_F16; c.act = CFSAR_ACT_NONE; c.relu = 0;
-    c.opath = vit_policy_opath(K, 1); c.store = vit_policy_store(0); c.group = vit_policy_group(K); c.colfast = vit_policy_colfast(K); c.dbg = 0;
+    c.pol = cfsar_vit_policy(kVitResidual, K); c.dbg = 0;
     c.hb_tokens = 0; c.hb_heads = 0; c.ha_tokens = ha_tokens;
 #ifdef CFSAR_DEV
     c.dbg = g_force_dbg & ((1 << 17) | (1 << 18));       // tile-height overrides only
@@ -1025,12 +978,7 @@ extern "C" int cfsar_gemm_residual_wide(const void* A, const void* W, void* x_hi
     c.part = nullptr; c.part_slots = 0; c.part_eps = 0.f;
     c.M = M; c.N = N; c.K = Kt; c.lda = lda; c.ldw = ldw; c.ldo = ldx; c.ldr = ldx;
     c.out_dtype = CFSAR_F16; c.in_dtype = CFSAR_F16; c.res_dtype = CFSAR_F16; c.act = CFSAR_ACT_NONE; c.relu = 0;
-#ifdef CFSAR_SPLIT_POLICY_BY_WALK
-    const int Kp = Kt;
-#else
-    const int Kp = K;                // (see gemm_lnfold_impl: the policies go by the operand's K)
-#endif
-    c.opath = vit_policy_opath(Kp, 2); c.store = vit_policy_store(0); c.group = vit_policy_group(Kp); c.colfast = vit_policy_colfast(Kp); c.dbg = 0;
+    c.pol = cfsar_vit_policy(kVitWide, K); c.dbg = 0;       // (see gemm_lnfold_impl: the policy goes by the operand's K)
     c.hb_tokens = 0; c.hb_heads = 0; c.ha_tokens = 0;
     c.ka = Ka; c.wide = 1; c.res_lo = x_lo; c.corr = corr; c.corr_tokens = corr_tokens;
 #ifdef CFSAR_DEV

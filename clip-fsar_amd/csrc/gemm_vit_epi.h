@@ -1,5 +1,4 @@
-// Shared device helpers and epilogues of the persistent ViT-block GEMM kernels (gemm_vit.hip: one 8-wave workgroup per CU, 256 x 256 tiles;
-// gemm_vit4.hip: two 4-wave workgroups per CU, 192 x 128 tiles).  Everything lives in an anonymous namespace: each translation unit gets its own copy.
+// Device helpers and epilogues of the persistent ViT-block GEMM kernel (gemm_vit.hip: one 8-wave workgroup per CU, 256 x 256 tiles).
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -20,16 +19,6 @@ template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
-
-// residual rows of an output tile's first pass fetched before its last K step on the LDS-DMA paths (A/B: -DCFSAR_PRE_OPATH1_ONLY)
-#ifdef CFSAR_PRE_OPATH1_ONLY
-constexpr int kPreMinOpath = 1, kPreMaxOpath = 1;
-#else
-constexpr int kPreMinOpath = 1, kPreMaxOpath = 2;
-#endif
-#ifndef CFSAR_EPI_PIPE
-#define CFSAR_EPI_PIPE 0      // 1 = software-pipelined epilogue stores (measured neutral to negative: profiles/r03_gemm_anatomy.md)
-#endif
 
 constexpr int kActRelu = 100;                   // internal: plain instance with ReLU (RN50 1x1 convs: relu(bn(conv)), few_shot.py:222-223)
 constexpr int TM = 256, TN = 256;              // output tile
@@ -80,11 +69,6 @@ __device__ __forceinline__ void glds16_asm_pol(const char* src, unsigned lds_add
 // instructions (clip-fsar_amd/build.py SOURCE_FLAGS; 0 of 1 500 stress launches against 44 of 150, same speed).  An earlier workaround
 // (pinning the transcendental operands with empty asm statements) is no longer needed and was removed.  Guards:
 // tests/test_gpu_kernels.py::test_gemm_lnfold_* and ::test_vit_gemms_are_bit_stable_under_a_second_stream, tools/stream_stress.py.
-#ifdef CFSAR_GELU_UNFUSED                      // A/B builds: row scale as its own multiply in front of quick_gelu4
-constexpr bool kGeluRowFused = false;
-#else
-constexpr bool kGeluRowFused = true;
-#endif
 __device__ __forceinline__ void quick_gelu4(float (&v)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -105,24 +89,12 @@ __device__ __forceinline__ float dpp_sum8(float v) {
     return v;
 }
 
-// 16-byte global store with a cache policy: 0 = default (write-back, line stays in this XCD's L2), 1 = nt, 2 = sc1 nt
-// (write-through: the line is not kept, MI355X_MICROARCH.md "stores of each flavour"; nt on top of it measured another 1 %)
+// 16-byte global store with a cache policy: 0 = default (write-back, line stays in this XCD's L2), 2 = sc1 nt (write-through: the line is
+// not kept, MI355X_MICROARCH.md "stores of each flavour"; nt on top of it measured another 1 %; the other flavours: profiles/r05_store_walk_ab.log)
 template <int POLICY>
 __device__ __forceinline__ void store16(void* dst, u32x4 v) {
-    if constexpr (POLICY == 1) {
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(dst));
-    } else if constexpr (POLICY == 2) {              // write-through + non-temporal (round 3: QKV 825 -> 814 us, c_fc 1180 -> 1171 us against sc1 alone)
+    if constexpr (POLICY == 2) {                     // write-through + non-temporal (round 3: QKV 825 -> 814 us, c_fc 1180 -> 1171 us against sc1 alone)
         asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-#ifdef CFSAR_DEV
-    } else if constexpr (POLICY == 3) {              // A/B only: write-through alone (the round-2 policy)
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-    } else if constexpr (POLICY == 4) {              // A/B only: system scope
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-    } else if constexpr (POLICY == 5) {              // A/B only: system scope + nt
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-    } else if constexpr (POLICY == 6) {              // A/B only: sc0
-        asm volatile("global_store_dwordx4 %0, %1, off sc0\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-#endif
     } else {
         *reinterpret_cast<u32x4*>(dst) = v;
     }
@@ -244,13 +216,11 @@ __device__ __forceinline__ void epilogue_rows(f32x16 (&acc)[NMI][2], const VitGe
         load_res(0);
     }
     // One 32-row pass = convert (8 groups of 4 values: [row scale] [activation] pack, ds_write_b64) -> read back (4 ds_read_b128) ->
-    // finish (4 x: [+ residual, statistics] 16-byte store).  CFSAR_EPI_PIPE = 1 (A/B builds) issues the four finish steps of pass
-    // mi - 1 BETWEEN the convert groups of pass mi; measured neutral (QKV, c_fc) to negative (residual instances): what the stores
-    // cost is not issue time inside the epilogue but memory-system interference with every workgroup's operand loads during the K
-    // loops that follow (profiles/r03_gemm_anatomy.md: workgroups that skip their stores slow down exactly like those that store).
+    // finish (4 x: [+ residual, statistics] 16-byte store).  Issuing the finish steps of pass mi - 1 between the convert groups of pass mi
+    // measured neutral to negative (profiles/r03_gemm_anatomy.md): the stores cost memory-system interference, not issue time.
     // per 32-row pass: k = -1.702 log2(e) / std and std of the pass's row (two registers live at a time)
     auto gelu_consts = [&](int mi, float& gk, float& gsd) __attribute__((always_inline)) {
-        if constexpr (kGeluRowFused && ROWSCALE && ACT == CFSAR_ACT_QUICKGELU) {
+        if constexpr (ROWSCALE && ACT == CFSAR_ACT_QUICKGELU) {
             float rs = rscale[mi];
             asm volatile("" : "+v"(rs));            // computed HERE, not hoisted into the K loop's last steps (24 spilled registers)
             gk = -1.702f * 1.4426950408889634f * rs;
@@ -261,9 +231,10 @@ __device__ __forceinline__ void epilogue_rows(f32x16 (&acc)[NMI][2], const VitGe
         const int ni = q >> 2, g = q & 3;
         TO4 o;
         float v[4];
-        if constexpr (kGeluRowFused && ROWSCALE && ACT == CFSAR_ACT_QUICKGELU) {
+        if constexpr (ROWSCALE && ACT == CFSAR_ACT_QUICKGELU) {
             // a / std * sigmoid(1.702 a / std) = a / (std + std * 2^(a * k)), k = -1.702 log2(e) / std: the row scale rides inside the
-            // sigmoid's denominator (one fma) instead of costing a multiply per element: 3 VALU + 2 transcendental instructions
+            // sigmoid's denominator (one fma) instead of costing a multiply per element: 3 VALU + 2 transcendental instructions (round 3, same
+            // box: c_fc 1 310 -> 1 299 us against the separate multiply)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float a = acc[mi][ni][4 * g + j];
@@ -363,35 +334,6 @@ __device__ __forceinline__ void epilogue_rows(f32x16 (&acc)[NMI][2], const VitGe
             }
         }
     };
-#if CFSAR_EPI_PIPE
-    u32x4 dprev[4], rvprev[4];
-#pragma unroll
-    for (int mi = 0; mi < NMI; ++mi) {
-        u32x4 rv[4];
-        if constexpr (HAS_RES) {
-#pragma unroll
-            for (int it = 0; it < 4; ++it) rv[it] = rvn[it];
-        }
-        if (mi < NMI - 1) load_res(mi + 1);
-        float gk = 0.f, gsd = 0.f;
-        gelu_consts(mi, gk, gsd);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            convert_group(mi, q, gk, gsd);
-            if (mi > 0 && (q & 1)) {
-                finish(mi - 1, q >> 1, dprev[q >> 1], rvprev[q >> 1]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        read_back(dprev);
-        if constexpr (HAS_RES) {
-#pragma unroll
-            for (int it = 0; it < 4; ++it) rvprev[it] = rv[it];
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < 4; ++it) finish(NMI - 1, it, dprev[it], rvprev[it]);
-#else
 #pragma unroll
     for (int mi = 0; mi < NMI; ++mi) {
         u32x4 rv[4];
@@ -409,7 +351,6 @@ __device__ __forceinline__ void epilogue_rows(f32x16 (&acc)[NMI][2], const VitGe
 #pragma unroll
         for (int it = 0; it < 4; ++it) finish(mi, it, d[it], rv[it]);
     }
-#endif
     if constexpr (COLSUM) {
         if (p.colsum != nullptr) {
             // sum over the 8 row groups rr (lanes differing in bits 3, 4, 5): row_ror:8, swizzle xor 16, bpermute xor 32 (integer adds: any order)
@@ -514,18 +455,6 @@ __device__ __forceinline__ void epilogue_rows_wide(f32x16 (&acc)[NMI][2], const 
         for (int it = 0; it < 2; ++it) {
             const f4 a = *reinterpret_cast<const f4*>(rd + it * 2 * CH + (((2 * Q) ^ rsw) << 4));
             const f4 b = *reinterpret_cast<const f4*>(rd + it * 2 * CH + (((2 * Q + 1) ^ rsw) << 4));
-#ifdef CFSAR_WIDE_PLAIN_C                                  // the plain C form (A/B: `python clip-fsar_amd/build.py --variant plainc -DCFSAR_WIDE_PLAIN_C`)
-            const h8 xh = __builtin_bit_cast(h8, rh[it]), xl = __builtin_bit_cast(h8, rl[it]);
-            h8 oh, ol;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = j < 4 ? a[j] : b[j - 4];
-                const float sum = d + ((float)xh[j] + (float)xl[j]);          // hi + lo is exact in fp32
-                const _Float16 h = (_Float16)sum;
-                oh[j] = h;
-                ol[j] = (_Float16)(sum - (float)h);
-            }
-#else
             // Per pair of elements: the stream's words enter the fp32 sum straight from their packed halves (v_fma_mix_f32: no fp16 -> fp32
             // conversion instructions), hi = one packed conversion, remainder = sum - hi again through v_fma_mix_f32 on the packed hi:
             // 4 VALU instructions per element where the plain C form compiled to 8, bit-identical results (the epilogue is VALU-bound: profiles/r04_gemm_plateau.md)
@@ -542,7 +471,6 @@ __device__ __forceinline__ void epilogue_rows_wide(f32x16 (&acc)[NMI][2], const 
                 olw[k] = __builtin_bit_cast(unsigned, lp);
             }
             const h8 oh = __builtin_bit_cast(h8, ohw), ol = __builtin_bit_cast(h8, olw);
-#endif
             const int step = mi * 2 + it;
             const bool rowok = FULL || mb + rr + step * 16 < p.M;
             if (p.stats_out) {                               // wave-uniform: statistics of the STORED hi words (what the consumer reads)

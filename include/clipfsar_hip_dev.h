@@ -16,13 +16,18 @@ extern "C" {
 #endif
 
 /* Force the kernel cfsar_gemm / cfsar_gemm_ex dispatch to (variant) and set the ablation bits (dbg) of the next launches;
- * (0, 0) restores the product policy.  Variants: see the dispatch comment in csrc/gemm.hip and csrc/gemm_vit.hip. */
+ * (0, 0) restores the product policy.  Every variant is a kernel the product library also runs (csrc/gemm.hip, dispatch comment):
+ *   1 = v1 (128 x 128, also the fp32 path), 2 = p3 (256 x 128), 12 / 13 = p12 / p12 persistent,
+ *   14 / 15 = skinny fp32 kernel always / never, 20 / 28 = the persistent ViT kernel (csrc/gemm_vit.hip) on any shape with the
+ *   register-staged / the early-DMA operand path. */
 void cfsar_debug_set_gemm_variant(int variant, int dbg);
 
-/* Operand path (0 register-staged, 1 LDS-DMA) and store policy (0 default, 1 nt, 2 sc1) of cfsar_gemm_lnfold /
- * cfsar_gemm_residual_stats; -1 = the product policy. */
-void cfsar_debug_set_vit_paths(int opath, int store);
-/* ablation bits of cfsar_gemm_lnfold (32 = bf16 MFMA instruction on the fp16 bits: timing A/B only) */
+/* Operand path of the persistent ViT kernel's launches (0 register-staged, 2 early LDS-DMA; 10 + path: K <= 1024 only);
+ * -1 = the product policy.  The store policy stays the product's. */
+void cfsar_debug_set_vit_paths(int opath);
+/* ablation bits of the ViT GEMM launches (csrc/gemm_vit.hip: 4 no epilogue, 8 every workgroup reads tile (0, 0), 16 no global
+ * stores, 128 start-time stagger, 1 << 17 / 1 << 18 192- / 256-row tiles, 1 << 21 / 1 << 22 forced paths skip the LN-folded / the
+ * residual launches; a few more load-policy / priority A/B bits are commented at their use) */
 void cfsar_debug_set_vit_dbg(int dbg);
 /* per-tile time stamps of the persistent ViT GEMM (device buffer [grid][64][4] of int64: s_memrealtime at tile start, K-loop end,
  * epilogue end; NULL = off) and the unit (x 64 cycles) of the start-time stagger that dbg bit 128 switches on */

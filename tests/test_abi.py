@@ -90,7 +90,7 @@ def test_no_cpu_fallback_in_product_path():
                 assert "clipfsar_oracle" not in src and "ref_harness" not in src, os.path.join(dirpath, f)
 
 
-def test_hot_kernels_use_no_scratch():
+def test_hot_kernels_keep_their_scratch_budgets():
     """Regression guard on the compiler's resource report (clip-fsar_amd/build.py writes build/resource_usage.json): the
     kernels of the ViT / RN50 hot path keep their working set in registers.  A run-time loop bound or a struct copy that
     sends an accumulator array to scratch is a 20-30 % slowdown that no parity test notices."""
@@ -124,7 +124,7 @@ def test_hot_kernels_use_no_scratch():
         # (round 3: 68 B without packed-fp32 VALU ops -- two more entry scalars)
         "gemm_kernel_p12IDF16bLi0ELb0E": 96, "gemm_kernel_p12IDF16bLi1ELb0E": 96, "gemm_kernel_p12IfLi0ELb1E": 128,
         "gemm_kernel_p12IDF16_Li0ELb1E": 128,              # fp16 residual stream (out_proj / c_proj of the bf16 mode)
-        "gemm_kernel_p10IDF16bLi0ELb0ELb0ELb0E": 0, "gemm_kernel_p10IfLi0ELb1ELb0ELb0E": 0,
+        "gemm_kernel_p10IDF16bLi0ELb0ELb0ELb1E": 8, "gemm_kernel_p10IfLi0ELb1ELb0ELb1E": 8,      # RN50 implicit 3x3 convs, Cout > 128
         "gemm_kernel_p3IDF16bDF16bLi0ELb0ELb0ELb1ELb0E": 0, "gemm_kernel_p3IDF16bDF16bLi0ELb0ELb0ELb1ELb1E": 0,   # RN50 implicit convs
         # the RN50 tower's fp16 mode (round 4): the same kernels on IEEE-half operands keep the bf16 instances' budgets
         "gemm_kernel_p3IDF16_DF16_Li0ELb0ELb0ELb1ELb0E": 0, "gemm_kernel_p3IDF16_DF16_Li0ELb0ELb0ELb1ELb1E": 0,
@@ -147,21 +147,3 @@ def test_hot_kernels_use_no_scratch():
         if "gemm_kernel_p6" in n or "gemm_kernel_p10" in n or "gemm_kernel_p12" in n:
             assert u.get("scratch", 0) <= 256, (n, u)
 
-
-def test_dev_only_gemm_forms_compile():
-    """csrc/gemm_vit4.hip and csrc/gemm_vit1w.hip (round 5's alternative GEMM forms, profiles/r05_gemm_forms.md) are part of the developer
-    library only; they must keep compiling for gfx950 next to the shared epilogue header, and the product source list must not carry them."""
-    import importlib.util
-    import subprocess
-    import tempfile
-    spec = importlib.util.spec_from_file_location("_cfsar_build_t", os.path.join(ROOT, "clip-fsar_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    assert set(mod.DEV_ONLY_SOURCES) == {"gemm_vit4.hip", "gemm_vit1w.hip"} and not set(mod.DEV_ONLY_SOURCES) & set(mod.SOURCES)
-    with tempfile.TemporaryDirectory() as td:
-        procs = [subprocess.Popen([mod.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DCFSAR_DEV"] + mod.NO_PACKED_FP32 +
-                                  ["-c", os.path.join(mod.CSRC, src), "-o", os.path.join(td, src + ".o")],
-                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for src in mod.DEV_ONLY_SOURCES]
-        for src, p in zip(mod.DEV_ONLY_SOURCES, procs):
-            out, _ = p.communicate()
-            assert p.returncode == 0, (src, out[-2000:])

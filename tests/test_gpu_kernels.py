@@ -534,9 +534,9 @@ def test_gemm_policy_reaches_every_kernel(hip, M, N, K):
 
 
 @pytest.mark.skipif(os.environ.get("CFSAR_DEV_LIB", "0") != "1", reason="developer library only (CFSAR_DEV_LIB=1)")
-@pytest.mark.parametrize("variant", [1, 2, 10, 11, 12, 13, 20, 21, 22, 24, 25, 26, 28, 30, 36, 38, 40, 42])
+@pytest.mark.parametrize("variant", [1, 2, 12, 13, 20, 28])
 def test_gemm_forced_variants_dev(hip, variant):
-    """Developer build: every kernel / operand path / store policy forced on ragged shapes (incl. shapes the policy would not
+    """Developer build: every kernel / operand path of the ViT kernel forced on ragged shapes (incl. shapes the policy would not
     give it), plus the alternative tile walks of the ViT kernel."""
     L = hip.lib()
     try:

@@ -1,6 +1,7 @@
 """Dev tool (GPU box): in-process A/B of GEMM variants on the ViT shapes.  Configs are interleaved round-robin so that clock /
 thermal drift hits all of them equally; reports the median and min over rounds.
-usage: python tools/gemm_ab.py B "variant:dbg" "variant:dbg" ...      (B = episodes -> M = 80*197*B)"""
+usage: python tools/gemm_ab.py B "variant:dbg" "variant:dbg" ...      (B = episodes -> M = 80*197*B)
+variants (include/clipfsar_hip_dev.h): 0 = product policy, 1 = v1, 2 = p3, 12 / 13 = p12 / persistent, 20 / 28 = the ViT kernel, register-staged / early-DMA"""
 import ctypes, os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["CFSAR_DEV_LIB"] = "1"      # the -DCFSAR_DEV library (clip-fsar_amd/build.py --dev) carries the variant hook

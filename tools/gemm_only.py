@@ -1,5 +1,6 @@
 """Dev tool: run ONE bf16 GEMM shape repeatedly (for rocprofv3 --pmc runs).
-usage: python tools/gemm_only.py M N K [plain|gelu|res16|res32]     env AB_VARIANT=v[:dbg] forces a kernel variant (dev library)"""
+usage: python tools/gemm_only.py M N K [plain|gelu|res16|res32]     env AB_VARIANT=v[:dbg] forces a kernel variant (dev library;
+the variants: include/clipfsar_hip_dev.h)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 var = os.environ.get("AB_VARIANT")

@@ -5,7 +5,7 @@ os.environ["CFSAR_DEV_LIB"] = "1"      # the -DCFSAR_DEV library (clip-fsar_amd/
 import torch
 from clip_fsar_amd import hip
 
-variants = [tuple(int(x) for x in (v.split(':') + ['0'])[:2]) for v in sys.argv[1:]] or [(1, 0), (2, 0), (6, 0), (10, 0)]
+variants = [tuple(int(x) for x in (v.split(':') + ['0'])[:2]) for v in sys.argv[1:]] or [(1, 0), (2, 0), (12, 0), (20, 0)]
 L = hip.lib()
 F = 640
 # (tag, M, N, K, residual)

@@ -1,5 +1,5 @@
 """Developer library: band-group size of the tile walk for the RN50 tower's 1 x 1 convs that run on the persistent ViT-block kernel (cfsar_gemm_ex
-dispatch, gemm.hip kVitGroup), bench leg of the rn50 configuration, alternated.  A walk A/B compares the same kernel instance, so it carries over to the
+dispatch, the group of gemm_vit.hip's cfsar_vit_policy), bench leg of the rn50 configuration, alternated.  A walk A/B compares the same kernel instance, so it carries over to the
 product build.  usage: CFSAR_DEV_LIB=1 python tools/rn_walk_ab.py [precision]"""
 import os
 import sys

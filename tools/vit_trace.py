@@ -1,6 +1,6 @@
 """Dev tool (GPU box): per-tile time stamps of the persistent ViT GEMM (csrc/gemm_vit.hip, CFSAR_TRACE) -- how long a tile's K loop
 and epilogue take on each CU and how synchronised the CUs are -- with and without a start-time stagger (dbg bit 128).
-usage: python tools/vit_trace.py [B=16] [shape=qkv|out|fc|proj] [variant=26] [stagger units ...]"""
+usage: python tools/vit_trace.py [B=16] [shape=qkv|out|fc|proj] [variant=28] [stagger units ...]     (variant 20 / 28: register-staged / early-DMA path)"""
 import ctypes, os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["CFSAR_DEV_LIB"] = "1"
@@ -9,7 +9,7 @@ from clip_fsar_amd import hip
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 shape = sys.argv[2] if len(sys.argv) > 2 else "qkv"
-variant = int(sys.argv[3]) if len(sys.argv) > 3 else 26
+variant = int(sys.argv[3]) if len(sys.argv) > 3 else 28
 staggers = [int(x) for x in sys.argv[4:]] or [0, 12, 23, 46]
 XDBG = int(os.environ.get("TRACE_DBG", "0"))          # extra ablation bits (16 = no stores, 4 = no epilogue)
 L = hip.lib()
@@ -25,7 +25,7 @@ bias = torch.randn(n, device=dev)
 res_mode = shape in ("out", "proj")
 out = torch.empty(M, n, device=dev, dtype=torch.float16 if res_mode else torch.bfloat16)
 act = hip.ACT_QUICKGELU if shape == "fc" else hip.ACT_NONE
-GRID, MAXT = int(os.environ.get("TRACE_GRID", "256")), 64          # TRACE_GRID=512: the two-workgroups-per-CU kernel (variants 36 / 38)
+GRID, MAXT = int(os.environ.get("TRACE_GRID", "256")), 64
 trace = torch.zeros(GRID * MAXT * 4, dtype=torch.int64, device=dev)
 
 
