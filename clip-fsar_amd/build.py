@@ -40,6 +40,12 @@ GALLERY_SOURCE = "gallery.hip"
 GALLERY_LIB = os.path.join(HERE, "libclipfsar_gallery.so")
 GALLERY_HEADER = os.path.join(os.path.dirname(HERE), "include", "clipfsar_gallery.h")
 GALLERY_USAGE = os.path.join(HERE, "build", "gallery", "resource_usage.json")
+# The text half of the gallery (include/clipfsar_gallery_text.h): the EVAL_TEXT / COMBINE kernels, a third library so that the two pinned
+# export sets stay as they are; same product path, flags and fence, its own staleness check and resource report.
+GALLERY_TEXT_SOURCE = "gallery_text.hip"
+GALLERY_TEXT_LIB = os.path.join(HERE, "libclipfsar_gallery_text.so")
+GALLERY_TEXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "clipfsar_gallery_text.h")
+GALLERY_TEXT_USAGE = os.path.join(HERE, "build", "gallery_text", "resource_usage.json")
 
 
 def _parse_usage(text: str) -> dict:
@@ -66,7 +72,7 @@ def _stale(lib=LIB) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f != GALLERY_SOURCE] + [
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in (GALLERY_SOURCE, GALLERY_TEXT_SOURCE)] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -77,46 +83,63 @@ def _stale(lib=LIB) -> bool:
 PACKED_LIB = os.path.join(HERE, "libclipfsar_hip_packed.so")
 
 
-def _gallery_stale() -> bool:
-    if not os.path.exists(GALLERY_LIB):
+def _side_stale(lib, source, header) -> bool:
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(GALLERY_LIB)
-    deps = [os.path.join(CSRC, GALLERY_SOURCE), os.path.join(CSRC, "common.h"), GALLERY_HEADER,
+    t = os.path.getmtime(lib)
+    deps = [os.path.join(CSRC, source), os.path.join(CSRC, "common.h"), header,
             os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]    # common.h includes the latter
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def _gallery_stale() -> bool:
+    return _side_stale(GALLERY_LIB, GALLERY_SOURCE, GALLERY_HEADER)
+
+
+def _build_side(source, lib, usage, verbose):
+    """one source -> its own library: the product FLAGS and the packed-fp32 fence, resource report -> usage"""
+    bdir = os.path.dirname(usage)
+    os.makedirs(bdir, exist_ok=True)
+    obj = os.path.join(bdir, source.replace(".hip", ".o"))
+    cmd = [HIPCC] + FLAGS + NO_PACKED_FP32 + ["-c", os.path.join(CSRC, source), "-o", obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if p.returncode != 0:
+        raise RuntimeError("hipcc failed on %s:\n%s" % (source, p.stdout))
+    rest = "\n".join(l for l in p.stdout.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l)
+    if verbose and rest.strip():
+        print(rest)
+    import json
+    with open(usage, "w") as f:
+        json.dump(_parse_usage(p.stdout), f, indent=0, sort_keys=True)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return lib
 
 
 def build_gallery(force: bool = False, verbose: bool = True) -> str:
     """libclipfsar_gallery.so from csrc/gallery.hip: the product FLAGS and the packed-fp32 fence, resource report -> GALLERY_USAGE"""
     if not force and not _gallery_stale():
         return GALLERY_LIB
-    bdir = os.path.dirname(GALLERY_USAGE)
-    os.makedirs(bdir, exist_ok=True)
-    obj = os.path.join(bdir, GALLERY_SOURCE.replace(".hip", ".o"))
-    cmd = [HIPCC] + FLAGS + NO_PACKED_FP32 + ["-c", os.path.join(CSRC, GALLERY_SOURCE), "-o", obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if p.returncode != 0:
-        raise RuntimeError("hipcc failed on %s:\n%s" % (GALLERY_SOURCE, p.stdout))
-    rest = "\n".join(l for l in p.stdout.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l)
-    if verbose and rest.strip():
-        print(rest)
-    import json
-    with open(GALLERY_USAGE, "w") as f:
-        json.dump(_parse_usage(p.stdout), f, indent=0, sort_keys=True)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", GALLERY_LIB, obj]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return GALLERY_LIB
+    return _build_side(GALLERY_SOURCE, GALLERY_LIB, GALLERY_USAGE, verbose)
+
+
+def build_gallery_text(force: bool = False, verbose: bool = True) -> str:
+    """libclipfsar_gallery_text.so from csrc/gallery_text.hip, as build_gallery; resource report -> GALLERY_TEXT_USAGE"""
+    if not force and not _side_stale(GALLERY_TEXT_LIB, GALLERY_TEXT_SOURCE, GALLERY_TEXT_HEADER):
+        return GALLERY_TEXT_LIB
+    return _build_side(GALLERY_TEXT_SOURCE, GALLERY_TEXT_LIB, GALLERY_TEXT_USAGE, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
-    The product build also builds the gallery library (build_gallery)."""
+    The product build also builds the gallery libraries (build_gallery, build_gallery_text)."""
     if not (dev or packed or variant):
         build_gallery(force=force, verbose=verbose)
+        build_gallery_text(force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT):
         return LIB_OUT

@@ -13,6 +13,9 @@ work is paid once, at registration.
 
 Every arithmetic step runs on the HIP kernels: the engine's tower (HipViT / HipResNet) and context2 (libclipfsar_hip.so), the support
 sequences, class means, norms, the gallery cosine + OTAM and the top-k (libclipfsar_gallery.so, clip_fsar_amd.gallery_hip).
+
+The head's other two eval branches, TRAIN.EVAL_TEXT (zero-shot text matching) and TRAIN.COMBINE (text probabilities fused with these
+OTAM logits), are served by clip_fsar_amd.text_gallery.TextGallery, which shares the machinery below (_GalleryBase).
 """
 from __future__ import annotations
 
@@ -27,14 +30,12 @@ def _flag(ns, name):
     return bool(hasattr(ns, name) and getattr(ns, name))
 
 
-class SupportGallery:
-    def __init__(self, head, device="cuda"):
-        head = getattr(head, "head", head)                 # BaseVideoModel -> its CNN_OTAM_CLIPFSAR head
+class _GalleryBase:
+    """What SupportGallery and TextGallery (clip_fsar_amd.text_gallery) share: the binding to the head's engine, class ids and their text
+    rows, the tower, context2 and the visual prototypes of the default eval branch."""
+
+    def _setup(self, head, device):
         cfg = head.args
-        for flag in ("EVAL_TEXT", "COMBINE"):
-            if _flag(cfg.TRAIN, flag):
-                raise NotImplementedError("SupportGallery: TRAIN.%s is not supported -- the gallery serves the default eval branch "
-                                          "(cosine + OTAM of context2 features, few_shot.py:2944-2990) only" % flag)
         self.head = head
         self.dev = torch.device(device)
         self.T = int(cfg.DATA.NUM_INPUT_FRAMES)
@@ -43,7 +44,10 @@ class SupportGallery:
         self._bind()
         self.E = int(self._engine.arch["embed"])
         self._qws = {}
-        self.clear()
+
+    @property
+    def _name(self):
+        return type(self).__name__
 
     # ------------------------------------------------------------------ engine binding
     def _bind(self):
@@ -55,8 +59,8 @@ class SupportGallery:
         invalidate_engine ...): old prototypes are never mixed with new weights."""
         eng = self.head._get_engine(self.dev)
         if eng is not self._engine or self.head._engine_key != self._engine_key:
-            raise RuntimeError("SupportGallery: the head's weights or text tables changed since these prototypes were computed; clear() "
-                               "the gallery and add the classes again")
+            raise RuntimeError("%s: the head's weights or text tables changed since these prototypes were computed; clear() "
+                               "the gallery and add the classes again" % self._name)
         return eng
 
     def fingerprint(self):
@@ -71,31 +75,6 @@ class SupportGallery:
     def class_ids(self):
         return list(self._ids)
 
-    def clear(self):
-        """Drop every class (and bind to the head's current engine)."""
-        self._bind()
-        self._ids = []
-        self._P = torch.empty(0, self.T, self.E, device=self.dev, dtype=torch.float32)      # prototypes [C, T, E]
-        self._pn = torch.empty(0, device=self.dev, dtype=torch.float32)                     # their frame-row norms [C * T]
-        self._text = torch.empty(0, self.E, device=self.dev, dtype=torch.float32)           # text row of every class [C, E]
-
-    def state_dict(self):
-        return {"fingerprint": self.fingerprint(), "class_ids": list(self._ids), "prototypes": self._P.cpu(), "norms": self._pn.cpu(),
-                "text": self._text.cpu()}
-
-    def load_state_dict(self, sd):
-        if sd["fingerprint"] != self.fingerprint():
-            raise ValueError("SupportGallery.load_state_dict: fingerprint %s does not match this gallery's %s" % (sd["fingerprint"],
-                                                                                                                    self.fingerprint()))
-        C = len(sd["class_ids"])
-        P, pn, text = sd["prototypes"], sd["norms"], sd["text"]
-        if tuple(P.shape) != (C, self.T, self.E) or tuple(pn.shape) != (C * self.T,) or tuple(text.shape) != (C, self.E):
-            raise ValueError("SupportGallery.load_state_dict: inconsistent shapes %s %s %s for %d classes" % (
-                tuple(P.shape), tuple(pn.shape), tuple(text.shape), C))
-        self._bind()
-        f32 = lambda t: t.to(device=self.dev, dtype=torch.float32).contiguous()
-        self._ids, self._P, self._pn, self._text = list(sd["class_ids"]), f32(P), f32(pn), f32(text)
-
     # ------------------------------------------------------------------ registration
     def _text_rows(self, eng, ids, text):
         """[n, E] fp32 device text rows of the new classes: TEST.CLASS_NAME rows (:2946), explicit [E] rows, or names through the text tower"""
@@ -105,15 +84,15 @@ class SupportGallery:
             src = text.get(cid) if text is not None else None
             if src is None:
                 if isinstance(cid, bool) or not isinstance(cid, int) or not 0 <= cid < n_test:
-                    raise ValueError("SupportGallery: class %r is not an index into TEST.CLASS_NAME (%d classes) and has no entry in `text`"
-                                     % (cid, n_test))
+                    raise ValueError("%s: class %r is not an index into TEST.CLASS_NAME (%d classes) and has no entry in `text`"
+                                     % (self._name, cid, n_test))
                 rows[i] = eng.text_test[cid]
             elif isinstance(src, str):
                 names[i] = src
             else:
                 t = torch.as_tensor(src).to(device=self.dev, dtype=torch.float32).reshape(-1)
                 if t.numel() != self.E:
-                    raise ValueError("SupportGallery: text row of class %r has %d values, expected %d" % (cid, t.numel(), self.E))
+                    raise ValueError("%s: text row of class %r has %d values, expected %d" % (self._name, cid, t.numel(), self.E))
                 rows[i] = t
         if names:
             enc = self._encode_names([names[i] for i in sorted(names)])
@@ -127,8 +106,8 @@ class SupportGallery:
         cfg = h.args
         src = getattr(cfg.VIDEO.HEAD, "TEXT_TOWER", None)
         if not src:
-            raise ValueError("SupportGallery: class names outside TEST.CLASS_NAME need VIDEO.HEAD.TEXT_TOWER (the text encoder); pass "
-                             "explicit [E] text rows instead")
+            raise ValueError("%s: class names outside TEST.CLASS_NAME need VIDEO.HEAD.TEXT_TOWER (the text encoder); pass "
+                             "explicit [E] text rows instead" % self._name)
         from . import text as ctext
         from .models.base.few_shot import _load_state_dict_file
         if src == "synthetic":
@@ -162,31 +141,32 @@ class SupportGallery:
 
     def _check_videos(self, videos, what):
         if not isinstance(videos, torch.Tensor) or not videos.is_cuda:
-            raise RuntimeError("SupportGallery: %s must be a HIP device tensor (no CPU path exists)" % what)
+            raise RuntimeError("%s: %s must be a HIP device tensor (no CPU path exists)" % (self._name, what))
         if videos.dim() != 5 or videos.shape[1] != self.T or videos.shape[2] != 3:
-            raise ValueError("SupportGallery: %s must be [N, T=%d, 3, H, W], got %s" % (what, self.T, tuple(videos.shape)))
+            raise ValueError("%s: %s must be [N, T=%d, 3, H, W], got %s" % (self._name, what, self.T, tuple(videos.shape)))
         return videos.to(dtype=torch.float32).contiguous()
 
-    def add_classes(self, videos, class_of_video, text=None):
-        """Register the classes of `videos` [Nv, T, 3, H, W] (fp32, device).  class_of_video [Nv]: the class id of every video -- an index into
-        TEST.CLASS_NAME (text row = text_features_test[id], few_shot.py:2946), or any hashable id with an entry in `text` ({id: class name
-        (encoded by the text tower) or [E] text row}).  Classes are appended in order of first appearance; any number of videos per class.
-        Returns the new classes' column indices."""
-        eng = self._fresh_engine()
-        videos = self._check_videos(videos, "videos")
-        ids_of_video = [c.item() if isinstance(c, torch.Tensor) else c for c in (
-            class_of_video.reshape(-1).cpu() if isinstance(class_of_video, torch.Tensor) else class_of_video)]
-        ids_of_video = [int(c) if isinstance(c, float) and c == int(c) else c for c in ids_of_video]
-        Nv = videos.shape[0]
-        if len(ids_of_video) != Nv:
-            raise ValueError("SupportGallery: %d videos but %d class ids" % (Nv, len(ids_of_video)))
-        new_ids = list(dict.fromkeys(ids_of_video))           # first-appearance order
-        dup = [c for c in new_ids if c in self._ids]
+    def _new_ids(self, ids, text):
+        """ids as plain hashables; raises on ids already registered and on a `text` that is not a dict"""
+        ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (ids.reshape(-1).cpu() if isinstance(ids, torch.Tensor) else ids)]
+        ids = [int(c) if isinstance(c, float) and c == int(c) else c for c in ids]
+        dup = [c for c in dict.fromkeys(ids) if c in self._ids]
         if dup:
-            raise ValueError("SupportGallery: class %r is already registered" % (dup[0],))
+            raise ValueError("%s: class %r is already registered" % (self._name, dup[0]))
         if text is not None and not isinstance(text, dict):
-            raise TypeError("SupportGallery: `text` must map class id -> class name or [E] text row")
-        trows = self._text_rows(eng, new_ids, text)
+            raise TypeError("%s: `text` must map class id -> class name or [E] text row" % self._name)
+        return ids
+
+    def _video_classes(self, videos, class_of_video, text):
+        """(class id of every video, the new classes in first-appearance order)"""
+        ids_of_video = self._new_ids(class_of_video, text)
+        if len(ids_of_video) != videos.shape[0]:
+            raise ValueError("%s: %d videos but %d class ids" % (self._name, videos.shape[0], len(ids_of_video)))
+        return ids_of_video, list(dict.fromkeys(ids_of_video))
+
+    def _prototypes(self, eng, videos, ids_of_video, new_ids, trows):
+        """The visual prototypes [n, T, E] of the new classes and their frame-row norms [n * T] (few_shot.py:2944-2962)"""
+        Nv = videos.shape[0]
         n = len(new_ids)
         local = {c: i for i, c in enumerate(new_ids)}
         order = sorted(range(Nv), key=lambda v: (local[ids_of_video[v]], v))     # videos grouped by class, video order inside a class
@@ -222,12 +202,7 @@ class SupportGallery:
         ghip.segment_mean(Y, offsets if not self.merge_before else torch.arange(n + 1, device=self.dev, dtype=torch.int32), P)
         pn = torch.empty(n * T, device=self.dev, dtype=torch.float32)
         ghip.row_norms(P, pn)
-        C0 = len(self._ids)
-        self._P = torch.cat([self._P, P]).contiguous()
-        self._pn = torch.cat([self._pn, pn]).contiguous()
-        self._text = torch.cat([self._text, trows]).contiguous()
-        self._ids.extend(new_ids)
-        return list(range(C0, C0 + n))
+        return P, pn
 
     # ------------------------------------------------------------------ classification
     def _query_ws(self, n):
@@ -237,6 +212,71 @@ class SupportGallery:
                       qn=torch.empty(n * self.T, device=self.dev, dtype=torch.float32))
             self._qws[n] = ws
         return ws
+
+    def topk(self, queries, k=5):
+        """(values [NQ, k] fp32 descending, class index [NQ, k] int32 into class_ids); ties go to the lower index"""
+        if not 1 <= k <= min(ghip.TOPK_MAX, max(1, len(self._ids))):
+            raise ValueError("%s.topk: k must be in [1, min(16, number of classes)], got %d" % (self._name, k))
+        logits = self.classify(queries)
+        values = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.float32)
+        index = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.int32)
+        ghip.topk(logits, k, values, index)
+        return values, index
+
+
+class SupportGallery(_GalleryBase):
+    def __init__(self, head, device="cuda"):
+        head = getattr(head, "head", head)                 # BaseVideoModel -> its CNN_OTAM_CLIPFSAR head
+        cfg = head.args
+        for flag in ("EVAL_TEXT", "COMBINE"):
+            if _flag(cfg.TRAIN, flag):
+                raise NotImplementedError("SupportGallery: TRAIN.%s is not supported -- the gallery serves the default eval branch "
+                                          "(cosine + OTAM of context2 features, few_shot.py:2944-2990) only; use "
+                                          "clip_fsar_amd.text_gallery.TextGallery for this branch" % flag)
+        self._setup(head, device)
+        self.clear()
+
+    def clear(self):
+        """Drop every class (and bind to the head's current engine)."""
+        self._bind()
+        self._ids = []
+        self._P = torch.empty(0, self.T, self.E, device=self.dev, dtype=torch.float32)      # prototypes [C, T, E]
+        self._pn = torch.empty(0, device=self.dev, dtype=torch.float32)                     # their frame-row norms [C * T]
+        self._text = torch.empty(0, self.E, device=self.dev, dtype=torch.float32)           # text row of every class [C, E]
+
+    def state_dict(self):
+        return {"fingerprint": self.fingerprint(), "class_ids": list(self._ids), "prototypes": self._P.cpu(), "norms": self._pn.cpu(),
+                "text": self._text.cpu()}
+
+    def load_state_dict(self, sd):
+        if sd["fingerprint"] != self.fingerprint():
+            raise ValueError("SupportGallery.load_state_dict: fingerprint %s does not match this gallery's %s" % (sd["fingerprint"],
+                                                                                                                    self.fingerprint()))
+        C = len(sd["class_ids"])
+        P, pn, text = sd["prototypes"], sd["norms"], sd["text"]
+        if tuple(P.shape) != (C, self.T, self.E) or tuple(pn.shape) != (C * self.T,) or tuple(text.shape) != (C, self.E):
+            raise ValueError("SupportGallery.load_state_dict: inconsistent shapes %s %s %s for %d classes" % (
+                tuple(P.shape), tuple(pn.shape), tuple(text.shape), C))
+        self._bind()
+        f32 = lambda t: t.to(device=self.dev, dtype=torch.float32).contiguous()
+        self._ids, self._P, self._pn, self._text = list(sd["class_ids"]), f32(P), f32(pn), f32(text)
+
+    def add_classes(self, videos, class_of_video, text=None):
+        """Register the classes of `videos` [Nv, T, 3, H, W] (fp32, device).  class_of_video [Nv]: the class id of every video -- an index into
+        TEST.CLASS_NAME (text row = text_features_test[id], few_shot.py:2946), or any hashable id with an entry in `text` ({id: class name
+        (encoded by the text tower) or [E] text row}).  Classes are appended in order of first appearance; any number of videos per class.
+        Returns the new classes' column indices."""
+        eng = self._fresh_engine()
+        videos = self._check_videos(videos, "videos")
+        ids_of_video, new_ids = self._video_classes(videos, class_of_video, text)
+        trows = self._text_rows(eng, new_ids, text)
+        P, pn = self._prototypes(eng, videos, ids_of_video, new_ids, trows)
+        C0, n = len(self._ids), len(new_ids)
+        self._P = torch.cat([self._P, P]).contiguous()
+        self._pn = torch.cat([self._pn, pn]).contiguous()
+        self._text = torch.cat([self._text, trows]).contiguous()
+        self._ids.extend(new_ids)
+        return list(range(C0, C0 + n))
 
     def classify(self, queries):
         """queries [NQ, T, 3, H, W] fp32 (device) -> logits [NQ, C] fp32 = -(OTAM + OTAM^T) against every registered class, in registration order"""
@@ -258,13 +298,3 @@ class SupportGallery:
             ghip.row_norms(Xq, ws["qn"])
             ghip.otam_gallery(Xq, ws["qn"], self._P, self._pn, logits[q0:q1], LAMBDA, self.single_direct)
         return logits
-
-    def topk(self, queries, k=5):
-        """(values [NQ, k] fp32 descending, class index [NQ, k] int32 into class_ids); ties go to the lower index"""
-        if not 1 <= k <= min(ghip.TOPK_MAX, max(1, len(self._ids))):
-            raise ValueError("SupportGallery.topk: k must be in [1, min(16, number of classes)], got %d" % k)
-        logits = self.classify(queries)
-        values = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.float32)
-        index = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.int32)
-        ghip.topk(logits, k, values, index)
-        return values, index
