@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -6,6 +6,7 @@ The .so is git-ignored but travels to the GPU box with the gpurun snapshot.
 """
 from __future__ import annotations
 
+import collections
 import os
 import subprocess
 import sys
@@ -34,18 +35,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
-# The support gallery (include/clipfsar_gallery.h): a library of its own, built on the product path beside libclipfsar_hip.so, with its own
-# staleness check and its own resource report (build/resource_usage.json stays the product library's).
-GALLERY_SOURCE = "gallery.hip"
-GALLERY_LIB = os.path.join(HERE, "libclipfsar_gallery.so")
-GALLERY_HEADER = os.path.join(os.path.dirname(HERE), "include", "clipfsar_gallery.h")
-GALLERY_USAGE = os.path.join(HERE, "build", "gallery", "resource_usage.json")
-# The text half of the gallery (include/clipfsar_gallery_text.h): the EVAL_TEXT / COMBINE kernels, a third library so that the two pinned
-# export sets stay as they are; same product path, flags and fence, its own staleness check and resource report.
-GALLERY_TEXT_SOURCE = "gallery_text.hip"
-GALLERY_TEXT_LIB = os.path.join(HERE, "libclipfsar_gallery_text.so")
-GALLERY_TEXT_HEADER = os.path.join(os.path.dirname(HERE), "include", "clipfsar_gallery_text.h")
-GALLERY_TEXT_USAGE = os.path.join(HERE, "build", "gallery_text", "resource_usage.json")
+# The side libraries: the support gallery (include/clipfsar_gallery.h) and its text half, the EVAL_TEXT / COMBINE kernels
+# (include/clipfsar_gallery_text.h).  Each is ONE source compiled with the product FLAGS and the fence into a library of its own beside
+# libclipfsar_hip.so (the three pinned export sets stay apart), with its own staleness check and its own resource report
+# (build/resource_usage.json stays the product library's).
+SideLib = collections.namedtuple("SideLib", "source lib usage")        # the C header (include/clipfsar_<name>.h) is a dependency through #include
+SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
+                           os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("gallery", "gallery_text")}
 
 
 def _parse_usage(text: str) -> dict:
@@ -68,12 +64,34 @@ def _parse_usage(text: str) -> dict:
     return out
 
 
-def _stale(lib=LIB) -> bool:
+def _includes(path, seen=None) -> set:
+    """the files a source reaches through #include "..." (csrc headers and the public headers of include/), itself included"""
+    import re
+    seen = set() if seen is None else seen
+    path = os.path.normpath(path)
+    if path not in seen:
+        seen.add(path)
+        for inc in re.findall(r'^#include "([^"]+)"', open(path).read(), flags=re.M):
+            _includes(os.path.join(os.path.dirname(path), inc), seen)
+    return seen
+
+
+def _side_deps(name) -> list:
+    return sorted(_includes(os.path.join(CSRC, SIDE_LIBS[name].source))) + [os.path.abspath(__file__)]
+
+
+def _product_deps() -> list:
+    """every file of csrc/ that is not a side library's source or a header only side libraries include"""
+    ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in SIDE_LIBS.values())) - ours
+    return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
+        os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
+
+
+def _stale(lib, deps) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in (GALLERY_SOURCE, GALLERY_TEXT_SOURCE)] + [
-        os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -83,99 +101,65 @@ def _stale(lib=LIB) -> bool:
 PACKED_LIB = os.path.join(HERE, "libclipfsar_hip_packed.so")
 
 
-def _side_stale(lib, source, header) -> bool:
-    if not os.path.exists(lib):
-        return True
-    t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, source), os.path.join(CSRC, "common.h"), header,
-            os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]    # common.h includes the latter
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def _gallery_stale() -> bool:
-    return _side_stale(GALLERY_LIB, GALLERY_SOURCE, GALLERY_HEADER)
-
-
-def _build_side(source, lib, usage, verbose):
-    """one source -> its own library: the product FLAGS and the packed-fp32 fence, resource report -> usage"""
-    bdir = os.path.dirname(usage)
-    os.makedirs(bdir, exist_ok=True)
-    obj = os.path.join(bdir, source.replace(".hip", ".o"))
-    cmd = [HIPCC] + FLAGS + NO_PACKED_FP32 + ["-c", os.path.join(CSRC, source), "-o", obj]
+def _compile(src, obj, extra, verbose) -> dict:
+    """hipcc -c one source of csrc/ with FLAGS + extra; the resource-usage remarks come back parsed, the compiler's other output is printed"""
+    cmd = [HIPCC] + FLAGS + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if p.returncode != 0:
-        raise RuntimeError("hipcc failed on %s:\n%s" % (source, p.stdout))
+        raise RuntimeError("hipcc failed on %s:\n%s" % (src, p.stdout))
     rest = "\n".join(l for l in p.stdout.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l)
     if verbose and rest.strip():
         print(rest)
+    return _parse_usage(p.stdout)
+
+
+def _link(lib, objs, usage, usage_path, verbose) -> str:
     import json
-    with open(usage, "w") as f:
-        json.dump(_parse_usage(p.stdout), f, indent=0, sort_keys=True)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj]
+    with open(usage_path, "w") as f:
+        json.dump(usage, f, indent=0, sort_keys=True)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return lib
 
 
-def build_gallery(force: bool = False, verbose: bool = True) -> str:
-    """libclipfsar_gallery.so from csrc/gallery.hip: the product FLAGS and the packed-fp32 fence, resource report -> GALLERY_USAGE"""
-    if not force and not _gallery_stale():
-        return GALLERY_LIB
-    return _build_side(GALLERY_SOURCE, GALLERY_LIB, GALLERY_USAGE, verbose)
-
-
-def build_gallery_text(force: bool = False, verbose: bool = True) -> str:
-    """libclipfsar_gallery_text.so from csrc/gallery_text.hip, as build_gallery; resource report -> GALLERY_TEXT_USAGE"""
-    if not force and not _side_stale(GALLERY_TEXT_LIB, GALLERY_TEXT_SOURCE, GALLERY_TEXT_HEADER):
-        return GALLERY_TEXT_LIB
-    return _build_side(GALLERY_TEXT_SOURCE, GALLERY_TEXT_LIB, GALLERY_TEXT_USAGE, verbose)
+def build_side(name, force: bool = False, verbose: bool = True) -> str:
+    """SIDE_LIBS[name]: its one source -> its own library with the product FLAGS and the packed-fp32 fence, resource report -> .usage"""
+    sl = SIDE_LIBS[name]
+    if not force and not _stale(sl.lib, _side_deps(name)):
+        return sl.lib
+    bdir = os.path.dirname(sl.usage)
+    os.makedirs(bdir, exist_ok=True)
+    obj = os.path.join(bdir, sl.source.replace(".hip", ".o"))
+    return _link(sl.lib, [obj], _compile(sl.source, obj, NO_PACKED_FP32, verbose), sl.usage, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
-    The product build also builds the gallery libraries (build_gallery, build_gallery_text)."""
+    The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        build_gallery(force=force, verbose=verbose)
-        build_gallery_text(force=force, verbose=verbose)
+        for name in SIDE_LIBS:
+            build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
-    if not force and not _stale(LIB_OUT):
+    if not force and not _stale(LIB_OUT, _product_deps()):
         return LIB_OUT
-    objs = []
-    procs = []
     bdir = os.path.join(HERE, "build", variant or "packed") if (packed or variant) else (os.path.join(HERE, "build", "dev") if dev else os.path.join(HERE, "build"))
     os.makedirs(bdir, exist_ok=True)
-    for src in SOURCES:
-        obj = os.path.join(bdir, src.replace(".hip", ".o"))
-        extra = (os.environ.get("CFSAR_BUILD_DEFS", "").split() if dev else []) + list(defs)      # developer A/B builds only
-        if packed or "-DCFSAR_PACKED_FP32" in extra:                                # A/B: compile with the packed instructions
-            extra = [e for e in extra if e != "-DCFSAR_PACKED_FP32"]
-        else:
-            extra = extra + SOURCE_FLAGS.get(src, [])
-        cmd = [HIPCC] + FLAGS + (["-DCFSAR_DEV"] if dev else []) + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-        objs.append(obj)
+    extra = (os.environ.get("CFSAR_BUILD_DEFS", "").split() if dev else []) + list(defs)          # developer A/B builds only
+    fenced = not (packed or "-DCFSAR_PACKED_FP32" in extra)                         # A/B: compile with the packed instructions
+    extra = (["-DCFSAR_DEV"] if dev else []) + [e for e in extra if e != "-DCFSAR_PACKED_FP32"]
+    objs = [os.path.join(bdir, src.replace(".hip", ".o")) for src in SOURCES]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(len(SOURCES)) as pool:                                  # every source at once: gemm.hip alone is most of the wall time
+        reports = list(pool.map(lambda so: _compile(so[0], so[1], extra + (SOURCE_FLAGS.get(so[0], []) if fenced else []), verbose),
+                                zip(SOURCES, objs)))
     usage = {}
-    for src, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError("hipcc failed on %s:\n%s" % (src, out))
-        usage.update(_parse_usage(out))
-        rest = "\n".join(l for l in out.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l)
-        if verbose and rest.strip():
-            print(rest)
-    import json
-    with open(USAGE if not (dev or packed or variant) else os.path.join(bdir, "resource_usage.json"), "w") as f:
-        json.dump(usage, f, indent=0, sort_keys=True)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_OUT] + objs
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return LIB_OUT
+    for r in reports:
+        usage.update(r)
+    return _link(LIB_OUT, objs, usage, USAGE if not (dev or packed or variant) else os.path.join(bdir, "resource_usage.json"), verbose)
 
 
 if __name__ == "__main__":

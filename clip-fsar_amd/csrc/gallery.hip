@@ -2,33 +2,12 @@
 // per-class means over contiguous runs of videos, row norms, top-k, and the hot kernel -- cos_sim + OTAM of every (query, class)
 // pair of a gallery (few_shot.py:1115-1124, 2657-2687, 2970-2990) as one exact-fp32 MFMA GEMM with the soft-min DPs in its epilogue.
 // A library of its own: libclipfsar_hip.so keeps exactly the entry points of include/clipfsar_hip.h.
-#include <stdarg.h>
-
-#include "common.h"
+#include "fp32_tile_gemm.h"
+#include "otam_dp.h"
+#include "side_lib.h"
 #include "../../include/clipfsar_gallery.h"
 
 namespace {
-
-thread_local char g_err[512] = {0};
-
-int fail(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
-#define CFSG_REQUIRE(cond, ...)               \
-    do {                                      \
-        if (!(cond)) return fail(__VA_ARGS__); \
-    } while (0)
 
 // ---- support sequences: one workgroup per output row (few_shot.py:2946, :2955)
 __global__ __launch_bounds__(128) void support_sequences_kernel(const float* __restrict__ feats, const float* __restrict__ text,
@@ -75,54 +54,12 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict_
     if (lane == 0) n[r] = sqrtf(ss);
 }
 
-// ---- OTAM soft-min DP: the recurrence of tail.hip's otam_dp (few_shot.py:2657-2687), un-stabilised like the reference, in the same
-// operation order, so equal distance blocks give bit-equal results.  The one difference is where the run-time-T rows live: `rstride`
-// floats apart in the caller's LDS slot instead of a fixed MAX_T + 2.
-constexpr int MAX_T = 32;
-template <int TT>
-__device__ __forceinline__ float otam_dp(const float* d /*[T][T] row stride rs, col stride cs*/, int rs, int cs, int Trt, float lbda,
-                                         float* rows, int rstride) {
-    const int T = TT > 0 ? TT : Trt;
-    // padded width M = T+2; columns 0 and T+1 are zero padding (few_shot.py:2663)
-    float regs[TT > 0 ? 2 * (TT + 2) : 1];
-    float* prev = TT > 0 ? regs : rows;
-    float* cur = TT > 0 ? regs + (TT + 2) : rows + rstride;
-    const float il = 1.0f / lbda;
-    prev[0] = 0.f;
-#pragma unroll
-    for (int m = 1; m <= T + 1; ++m) {                      // first row: running sum (:2668-2671)
-        const float dv = (m <= T) ? d[0 * rs + (m - 1) * cs] : 0.f;
-        prev[m] = dv + prev[m - 1];
-    }
-#pragma unroll
-    for (int l = 1; l < T; ++l) {
-        cur[0] = 0.f;
-        {   // first non-zero column (:2675)
-            const float dv = d[l * rs + 0 * cs];
-            cur[1] = dv - lbda * logf(expf(-prev[0] * il) + expf(-prev[1] * il) + expf(-cur[0] * il));
-        }
-#pragma unroll
-        for (int m = 2; m <= T; ++m) {                      // middle columns (:2678-2679)
-            const float dv = d[l * rs + (m - 1) * cs];
-            cur[m] = dv - lbda * logf(expf(-prev[m - 1] * il) + expf(-cur[m - 1] * il));
-        }
-        // last (padding) column (:2683)
-        cur[T + 1] = 0.f - lbda * logf(expf(-prev[T] * il) + expf(-prev[T + 1] * il) + expf(-cur[T] * il));
-#pragma unroll
-        for (int m = 0; m <= T + 1; ++m) prev[m] = cur[m];
-    }
-    return prev[T + 1];
-}
-
 // ---- cos_sim + OTAM of a gallery.  A workgroup (4 waves) owns QB queries x QB classes: a TILE x TILE block of frame rows
 // (T = 8: 8 x 8 videos, 64 pairs; T = 16: 4 x 4).
-//   GEMM: [QB*T, E] x [QB*T, E]^T with v_mfma_f32_16x16x4_f32 (an exact fp32 fmaf chain per k step); both operands staged through LDS in
-//   BK-float chunks, the next chunk's global loads in flight while the current one is multiplied.  Wave w owns the 32 x 32 quarter
-//   (w >> 1, w & 1) as 2 x 2 MFMA tiles.  Inside a chunk, MFMA step s of lane half h takes k = 8h + s: every lane reads its k values as
-//   two ds_read_b128 per tile (A and B use the same k map, so the products are those of the plain GEMM, summed in another order).
+//   GEMM: [QB*T, E] x [QB*T, E]^T, fp32_tile_gemm (fp32_tile_gemm.h).
 //   Epilogue: d = 1 - dot / (qn pn + 0.01) into an LDS image of the tile (aliasing the staging buffers), then one lane per
 //   (pair, direction) runs the DP -- rows in registers for T = 8 / 16, in an LDS slot per thread for run-time T.
-constexpr int TILE = 64, BK = 32, SLD = BK + 4 /* staging row stride: 16-B aligned rows */, DLD = TILE + 1 /* distance image */;
+constexpr int DLD = TILE + 1 /* distance image */;
 constexpr int MAX_PAIRS = 256;
 
 __host__ __device__ inline int tile_videos(int T) { return TILE / T < 16 ? TILE / T : 16; }
@@ -133,10 +70,6 @@ __host__ __device__ inline int dp_slots(int T) {
 // LDS floats: staging (A | B; the distance image reuses it) + norms + DP results (+ run-time-T DP rows)
 __host__ __device__ inline int gallery_lds_floats(int T, bool fixed_t) {
     return 2 * TILE * SLD + 2 * TILE + 2 * MAX_PAIRS + (fixed_t ? 0 : dp_slots(T) * 2 * (T + 2));
-}
-
-__device__ __forceinline__ float4 load_row4(const float* __restrict__ X, size_t row, int col, int E, bool ok) {
-    return ok ? *reinterpret_cast<const float4*>(X + row * E + col) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 template <int TT>
@@ -162,52 +95,9 @@ __global__ __launch_bounds__(256) void otam_gallery_kernel(const float* __restri
     if (tid < TILE) sqn[tid] = tid < a_rows ? qn[arow0 + tid] : 1.f;
     else if (tid < 2 * TILE) spn[tid - TILE] = tid - TILE < b_rows ? pn[brow0 + tid - TILE] : 1.f;
 
-    // staging: 2 float4 of A and 2 of B per thread and chunk; rows / columns outside the operands are zero (they add +0 to the sums)
-    const int sr0 = tid >> 3, sr1 = (tid + 256) >> 3, sc = (tid & 7) * 4;          // staged rows of the two float4s, their column
-    float4 ra0, ra1, rb0, rb1;
-#define CFSG_LOAD_CHUNK(k0)                                                                                  \
-    do {                                                                                                     \
-        const int col_ = (k0) + sc;                                                                          \
-        ra0 = load_row4(Xq, arow0 + sr0, col_, E, sr0 < a_rows && col_ < E);                                 \
-        ra1 = load_row4(Xq, arow0 + sr1, col_, E, sr1 < a_rows && col_ < E);                                 \
-        rb0 = load_row4(P, brow0 + sr0, col_, E, sr0 < b_rows && col_ < E);                                  \
-        rb1 = load_row4(P, brow0 + sr1, col_, E, sr1 < b_rows && col_ < E);                                  \
-    } while (0)
     f32x4 acc[2][2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+    fp32_tile_gemm(Xq, arow0, a_rows, P, brow0, b_rows, E, sA, sB, acc);      // ends with a barrier: the distance image overwrites the staging buffers
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, fr = lane & 15, fh = lane >> 4;
-    CFSG_LOAD_CHUNK(0);
-    for (int k0 = 0; k0 < E; k0 += BK) {
-        __syncthreads();                                                  // the previous chunk's fragment reads are done
-        *reinterpret_cast<float4*>(sA + sr0 * SLD + sc) = ra0;
-        *reinterpret_cast<float4*>(sA + sr1 * SLD + sc) = ra1;
-        *reinterpret_cast<float4*>(sB + sr0 * SLD + sc) = rb0;
-        *reinterpret_cast<float4*>(sB + sr1 * SLD + sc) = rb1;
-        __syncthreads();
-        if (k0 + BK < E) CFSG_LOAD_CHUNK(k0 + BK);                                   // next chunk in flight during this one's MFMAs
-        f32x4 a[2][2], b[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float* pa = sA + (wm + 16 * i + fr) * SLD + fh * 8;
-            const float* pb = sB + (wn + 16 * i + fr) * SLD + fh * 8;
-            a[i][0] = *reinterpret_cast<const f32x4*>(pa);
-            a[i][1] = *reinterpret_cast<const f32x4*>(pa + 4);
-            b[i][0] = *reinterpret_cast<const f32x4*>(pb);
-            b[i][1] = *reinterpret_cast<const f32x4*>(pb + 4);
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][s >> 2][s & 3], b[ni][s >> 2][s & 3], acc[mi][ni], 0, 0, 0);
-    }
-#undef CFSG_LOAD_CHUNK
-    __syncthreads();                                                      // the distance image overwrites the staging buffers
     // C/D map of the 16x16 MFMA: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -300,10 +190,10 @@ extern "C" const char* cfsg_last_error(void) { return g_err; }
 
 extern "C" int cfsg_support_sequences(const float* feats, const float* text, const int32_t* cls_of_video, float* X, int Nv, int T, int E,
                                       int n_cls, cfsg_stream_t stream) {
-    CFSG_REQUIRE(feats && text && cls_of_video && X, "cfsg_support_sequences: null pointer");
-    CFSG_REQUIRE(Nv > 0 && T > 0 && E > 0 && n_cls > 0, "cfsg_support_sequences: bad shape (Nv=%d T=%d E=%d n_cls=%d)", Nv, T, E, n_cls);
+    SIDE_REQUIRE(feats && text && cls_of_video && X, "cfsg_support_sequences: null pointer");
+    SIDE_REQUIRE(Nv > 0 && T > 0 && E > 0 && n_cls > 0, "cfsg_support_sequences: bad shape (Nv=%d T=%d E=%d n_cls=%d)", Nv, T, E, n_cls);
     const long long rows = (long long)Nv * (T + 1);
-    CFSG_REQUIRE(rows <= 0x7fffffffLL, "cfsg_support_sequences: %lld rows", rows);
+    SIDE_REQUIRE(rows <= 0x7fffffffLL, "cfsg_support_sequences: %lld rows", rows);
     hipLaunchKernelGGL(support_sequences_kernel, dim3((unsigned)rows), dim3(128), 0, static_cast<hipStream_t>(stream), feats, text,
                        cls_of_video, X, T, E, n_cls);
     return check_launch("cfsg_support_sequences");
@@ -311,35 +201,35 @@ extern "C" int cfsg_support_sequences(const float* feats, const float* text, con
 
 extern "C" int cfsg_segment_mean(const float* X, const int32_t* offsets, float* out, int Nv, int L, int E, int C, int rows_kept,
                                  cfsg_stream_t stream) {
-    CFSG_REQUIRE(X && offsets && out, "cfsg_segment_mean: null pointer");
-    CFSG_REQUIRE(Nv > 0 && L > 0 && E > 0 && C > 0 && rows_kept > 0 && rows_kept <= L,
+    SIDE_REQUIRE(X && offsets && out, "cfsg_segment_mean: null pointer");
+    SIDE_REQUIRE(Nv > 0 && L > 0 && E > 0 && C > 0 && rows_kept > 0 && rows_kept <= L,
                  "cfsg_segment_mean: bad shape (Nv=%d L=%d E=%d C=%d rows_kept=%d)", Nv, L, E, C, rows_kept);
     const long long blocks = (long long)C * rows_kept;
-    CFSG_REQUIRE(blocks <= 0x7fffffffLL, "cfsg_segment_mean: %lld output rows", blocks);
+    SIDE_REQUIRE(blocks <= 0x7fffffffLL, "cfsg_segment_mean: %lld output rows", blocks);
     hipLaunchKernelGGL(segment_mean_kernel, dim3((unsigned)blocks), dim3(128), 0, static_cast<hipStream_t>(stream), X, offsets, out, Nv, L,
                        E, rows_kept);
     return check_launch("cfsg_segment_mean");
 }
 
 extern "C" int cfsg_row_norms(const float* X, float* n, int R, int E, cfsg_stream_t stream) {
-    CFSG_REQUIRE(X && n, "cfsg_row_norms: null pointer");
-    CFSG_REQUIRE(R > 0 && E > 0, "cfsg_row_norms: bad shape (R=%d E=%d)", R, E);
+    SIDE_REQUIRE(X && n, "cfsg_row_norms: null pointer");
+    SIDE_REQUIRE(R > 0 && E > 0, "cfsg_row_norms: bad shape (R=%d E=%d)", R, E);
     hipLaunchKernelGGL(row_norms_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), X, n, R, E);
     return check_launch("cfsg_row_norms");
 }
 
 extern "C" int cfsg_otam_gallery(const float* Xq, const float* qn, const float* P, const float* pn, float* logits, float* dists_out, int NQ,
                                  int C, int T, int E, float lambda, int single_direct, cfsg_stream_t stream) {
-    CFSG_REQUIRE(Xq && qn && P && pn && logits, "cfsg_otam_gallery: null pointer");
-    CFSG_REQUIRE(NQ > 0 && C > 0 && T > 0 && T <= MAX_T && E >= 4 && E <= 8192 && E % 4 == 0,
+    SIDE_REQUIRE(Xq && qn && P && pn && logits, "cfsg_otam_gallery: null pointer");
+    SIDE_REQUIRE(NQ > 0 && C > 0 && T > 0 && T <= MAX_T && E >= 4 && E <= 8192 && E % 4 == 0,
                  "cfsg_otam_gallery: bad shape (NQ=%d C=%d T=%d E=%d; T <= 32, E %% 4 == 0, 4 <= E <= 8192)", NQ, C, T, E);
-    CFSG_REQUIRE(lambda > 0.f, "cfsg_otam_gallery: lambda must be > 0");
+    SIDE_REQUIRE(lambda > 0.f, "cfsg_otam_gallery: lambda must be > 0");
     const int qb = tile_videos(T);
     const long long gx = ((long long)C + qb - 1) / qb, gy = ((long long)NQ + qb - 1) / qb;
-    CFSG_REQUIRE(gy <= 65535, "cfsg_otam_gallery: NQ=%d too large for one launch (at most %d at T=%d)", NQ, 65535 * qb, T);
+    SIDE_REQUIRE(gy <= 65535, "cfsg_otam_gallery: NQ=%d too large for one launch (at most %d at T=%d)", NQ, 65535 * qb, T);
     const bool fixed_t = T == 8 || T == 16;                   // DP rows in registers; otherwise in an LDS slot per thread
     const int lds = gallery_lds_floats(T, fixed_t) * (int)sizeof(float);
-    CFSG_REQUIRE(lds <= 48 * 1024, "cfsg_otam_gallery: LDS %d bytes", lds);
+    SIDE_REQUIRE(lds <= 48 * 1024, "cfsg_otam_gallery: LDS %d bytes", lds);
     auto launch = [&](auto kern) -> int {
         hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, static_cast<hipStream_t>(stream), Xq, qn, P, pn, logits,
                            dists_out, NQ, C, T, E, lambda, single_direct);
@@ -351,8 +241,8 @@ extern "C" int cfsg_otam_gallery(const float* Xq, const float* qn, const float* 
 }
 
 extern "C" int cfsg_topk(const float* logits, float* values, int32_t* index, int NQ, int C, int k, cfsg_stream_t stream) {
-    CFSG_REQUIRE(logits && values && index, "cfsg_topk: null pointer");
-    CFSG_REQUIRE(NQ > 0 && C > 0 && C <= 65535 && k >= 1 && k <= KMAX && k <= C,
+    SIDE_REQUIRE(logits && values && index, "cfsg_topk: null pointer");
+    SIDE_REQUIRE(NQ > 0 && C > 0 && C <= 65535 && k >= 1 && k <= KMAX && k <= C,
                  "cfsg_topk: bad shape (NQ=%d C=%d k=%d; 1 <= k <= 16, k <= C <= 65535)", NQ, C, k);
     hipLaunchKernelGGL(topk_kernel, dim3((unsigned)NQ), dim3(64), 0, static_cast<hipStream_t>(stream), logits, values, index, C, k);
     return check_launch("cfsg_topk");

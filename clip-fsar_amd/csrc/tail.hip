@@ -2,6 +2,7 @@
 // aux class logits, sequence building (text-token concat, optional class merge), short-sequence attention of the
 // temporal transformer, prototypes, and cosine + OTAM -> logits.  All kernels take a batch of episodes.
 #include "common.h"
+#include "otam_dp.h"
 
 namespace {
 
@@ -320,46 +321,7 @@ __global__ __launch_bounds__(128) void prototypes_kernel(const float* __restrict
 
 // ---- A13/A14/A15 cos_sim + OTAM both directions -> logits.  One workgroup per (b, q).
 //   LDS: query rows [T][E], sim [way][T][T].  Each wave computes dot products (wave-shuffle reduction over E),
-//   then 2*way threads run the sequential soft-min DP (few_shot.py:2657-2687), un-stabilised like the reference.
-constexpr int MAX_T = 32;
-// TT > 0: T is the compile-time constant TT, every loop unrolls and the two DP rows live in registers.  TT == 0: run-time T, the
-// rows live in the caller's LDS scratch `rows` (2 x (MAX_T + 2) floats per thread) -- never in scratch memory: the recurrence is
-// one dependent chain of T*T cells, and a scratch round trip per cell made this kernel 140 us for an 8x8 problem.
-template <int TT>
-__device__ __forceinline__ float otam_dp(const float* d /*[T][T] row-major, row stride rs, col stride cs*/, int rs, int cs, int Trt,
-                                         float lbda, float* rows) {
-    const int T = TT > 0 ? TT : Trt;
-    // padded width M = T+2; columns 0 and T+1 are zero padding (few_shot.py:2663)
-    float regs[TT > 0 ? 2 * (TT + 2) : 1];
-    float* prev = TT > 0 ? regs : rows;
-    float* cur = TT > 0 ? regs + (TT + 2) : rows + (MAX_T + 2);
-    const float il = 1.0f / lbda;
-    prev[0] = 0.f;
-#pragma unroll
-    for (int m = 1; m <= T + 1; ++m) {                      // first row: running sum (:2668-2671)
-        const float dv = (m <= T) ? d[0 * rs + (m - 1) * cs] : 0.f;
-        prev[m] = dv + prev[m - 1];
-    }
-#pragma unroll
-    for (int l = 1; l < T; ++l) {
-        cur[0] = 0.f;
-        {   // first non-zero column (:2675)
-            const float dv = d[l * rs + 0 * cs];
-            cur[1] = dv - lbda * logf(expf(-prev[0] * il) + expf(-prev[1] * il) + expf(-cur[0] * il));
-        }
-#pragma unroll
-        for (int m = 2; m <= T; ++m) {                      // middle columns (:2678-2679)
-            const float dv = d[l * rs + (m - 1) * cs];
-            cur[m] = dv - lbda * logf(expf(-prev[m - 1] * il) + expf(-cur[m - 1] * il));
-        }
-        // last (padding) column (:2683)
-        cur[T + 1] = 0.f - lbda * logf(expf(-prev[T] * il) + expf(-prev[T + 1] * il) + expf(-cur[T] * il));
-#pragma unroll
-        for (int m = 0; m <= T + 1; ++m) prev[m] = cur[m];
-    }
-    return prev[T + 1];
-}
-
+//   then 2*way threads run the sequential soft-min DP (otam_dp.h).
 // One workgroup per (query video, class): LDS holds the query's T frames [T][E], their norms and the T x T distance block.
 // Phase 1: each wave takes support frames j = wave, wave + 4, ...: the frame's E values sit in registers (float4 per lane per
 // 256 columns, E <= 2048), its T dot products accumulate side by side from ds_read_b128s of the query rows and are reduced at
@@ -431,8 +393,8 @@ __global__ __launch_bounds__(256) void cos_otam_kernel(const float* __restrict__
     if (tid < 2) {
         float v = 0.f;
         float* rows = dprows + (TT > 0 ? 0 : tid * 2 * (MAX_T + 2));
-        if (tid == 0) v = otam_dp<TT>(sd, T, 1, T, lbda, rows);
-        else if (!single_direct) v = otam_dp<TT>(sd, 1, T, T, lbda, rows);        // transposed distances (:2982)
+        if (tid == 0) v = otam_dp<TT>(sd, T, 1, T, lbda, rows, MAX_T + 2);
+        else if (!single_direct) v = otam_dp<TT>(sd, 1, T, T, lbda, rows, MAX_T + 2);        // transposed distances (:2982)
         res[tid] = v;
     }
     __syncthreads();

@@ -11,7 +11,7 @@ import os
 
 import torch  # noqa: F401  (imported first so that torch's HIP runtime is the one the library binds to)
 
-from . import hip
+from . import _cabi, hip
 
 ABI_VERSION = 1          # CFSG_ABI_VERSION of include/clipfsar_gallery.h this file's SIGNATURES were written against
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libclipfsar_gallery.so")
@@ -36,34 +36,13 @@ def lib():
     """Load (once) and return the ctypes handle.  Raises when the library is not built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError("clip_fsar_amd: %s is missing -- build it with `python clip-fsar_amd/build.py` (hipcc --offload-arch=gfx950). "
-                               "There is no CPU/PyTorch fallback for the gallery." % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _c_int
-        L.cfsg_last_error.restype = ctypes.c_char_p
-        L.cfsg_last_error.argtypes = []
-        if L.cfsg_abi_version() != ABI_VERSION:
-            raise RuntimeError("clip_fsar_amd: %s has ABI revision %d, this binding was written against %d -- rebuild it "
-                               "(python clip-fsar_amd/build.py --force)" % (LIB_PATH, L.cfsg_abi_version(), ABI_VERSION))
-        _lib = L
+        _lib = _cabi.load(LIB_PATH, SIGNATURES, "cfsg_", ABI_VERSION, "the gallery")
     return _lib
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed: %s" % (what, lib().cfsg_last_error().decode(errors="replace")))
-
-
+_check = _cabi.checker(lib, "cfsg_")
+_shape = _cabi.shape_checker("gallery_hip")
 _dev, _stream = hip._dev, hip._stream
-
-
-def _shape(t, shape, name):
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("clip_fsar_amd.gallery_hip: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
 
 
 def support_sequences(feats, text, cls_of_video, X):

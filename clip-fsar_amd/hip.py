@@ -10,6 +10,8 @@ import os
 
 import torch  # noqa: F401  (imported first so that torch's libamdhip64.so.7 is the HIP runtime the library binds to)
 
+from . import _cabi
+
 F32, BF16, F16 = 0, 1, 2
 ABI_VERSION = 9          # CFSAR_ABI_VERSION of include/clipfsar_hip.h this file's SIGNATURES were written against
 ACT_NONE, ACT_QUICKGELU, ACT_GELU_ERF = 0, 1, 2
@@ -80,20 +82,7 @@ def lib():
     """Load (once) and return the ctypes handle.  Raises loudly when the HIP extension is not built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "clip_fsar_amd: HIP extension %s is missing -- build it with `python clip-fsar_amd/build.py` "
-                "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for the hot path." % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = args
-            fn.restype = _c_int
-        L.cfsar_last_error.restype = ctypes.c_char_p
-        L.cfsar_last_error.argtypes = []
-        if L.cfsar_abi_version() != ABI_VERSION:
-            raise RuntimeError("clip_fsar_amd: %s has ABI revision %d, this binding was written against %d -- rebuild it "
-                               "(python clip-fsar_amd/build.py --force)" % (LIB_PATH, L.cfsar_abi_version(), ABI_VERSION))
+        L = _cabi.load(LIB_PATH, SIGNATURES, "cfsar_", ABI_VERSION, "the hot path")
         if DEV_LIB:
             L.cfsar_debug_set_gemm_variant.argtypes = [ctypes.c_int, ctypes.c_int]
             L.cfsar_debug_set_gemm_variant.restype = None
@@ -109,9 +98,7 @@ def lib():
     return _lib
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed: %s" % (what, lib().cfsar_last_error().decode(errors="replace")))
+_check = _cabi.checker(lib, "cfsar_")
 
 
 def _dev_ptr(t, dtype=None, name="tensor"):

@@ -3,19 +3,14 @@ the ctypes signatures in clip_fsar_amd/hip.py have the arity of the header proto
 import os
 import re
 
+from _abi import _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_hip.h")
 
 
 def _header_prototypes():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(?:int|const char\*)\s*(cfsar_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S):
-        args = m.group(2).strip()
-        n = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-        protos[m.group(1)] = n
-    return protos
+    return _prototypes(HEADER, "cfsar_")
 
 
 def test_header_symbols_exported_and_arity_matches():

@@ -3,29 +3,14 @@ header, validates arguments without a GPU, keeps its hot kernel out of scratch; 
 import ctypes
 import json
 import os
-import re
-import subprocess
 
 import pytest
+
+from _abi import _exported, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_gallery.h")
 HIP_HEADER = os.path.join(ROOT, "include", "clipfsar_hip.h")
-
-
-def _prototypes(path, prefix):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(?:int|const char\*)\s*(%s\w+)\s*\(([^;]*?)\)\s*;" % prefix, text, flags=re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return protos
-
-
-def _exported(lib_path):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], stdout=subprocess.PIPE, text=True, check=True).stdout
-    syms = {l.split()[-1] for l in out.splitlines() if l.strip()}
-    return {s for s in syms if not s.startswith(("__hip", "_init", "_fini", "__bss", "_edata", "_end"))}
 
 
 @pytest.fixture(scope="module")
@@ -91,14 +76,14 @@ def test_python_wrappers_reject_cpu_tensors(glib):
 
 def test_gallery_kernels_use_no_scratch_and_stay_out_of_the_product_report(glib):
     from clip_fsar_amd import build as b
-    if not os.path.exists(b.GALLERY_USAGE):
-        b.build_gallery(force=True, verbose=False)
-    usage = json.load(open(b.GALLERY_USAGE))
+    if not os.path.exists(b.SIDE_LIBS["gallery"].usage):
+        b.build_side("gallery", force=True, verbose=False)
+    usage = json.load(open(b.SIDE_LIBS["gallery"].usage))
     otam = [n for n in usage if "otam_gallery_kernel" in n]
     assert len(otam) == 3, sorted(usage)                  # T = 8, T = 16, run-time T
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0, (n, u)
-    assert b.GALLERY_SOURCE not in b.SOURCES and b.GALLERY_USAGE != b.USAGE
+    assert b.SIDE_LIBS["gallery"].source not in b.SOURCES and b.SIDE_LIBS["gallery"].usage != b.USAGE
     if os.path.exists(b.USAGE):
         assert not any("otam_gallery_kernel" in n for n in json.load(open(b.USAGE)))
 

@@ -5,28 +5,14 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 from types import SimpleNamespace as NS
 
 import pytest
 
+from _abi import _exported, _prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_gallery_text.h")
-
-
-def _prototypes(path, prefix):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(?:int|const char\*)\s*(%s\w+)\s*\(([^;]*?)\)\s*;" % prefix, text, flags=re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ("", "void") else len([a for a in args.split(",") if a.strip()])
-    return protos
-
-
-def _exported(lib_path):
-    out = subprocess.run(["nm", "-D", "--defined-only", lib_path], stdout=subprocess.PIPE, text=True, check=True).stdout
-    syms = {l.split()[-1] for l in out.splitlines() if l.strip()}
-    return {s for s in syms if not s.startswith(("__hip", "_init", "_fini", "__bss", "_edata", "_end"))}
 
 
 @pytest.fixture(scope="module")
@@ -100,29 +86,41 @@ def test_python_wrappers_reject_cpu_tensors(tlib):
 
 def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(tlib):
     from clip_fsar_amd import build as b
-    if not os.path.exists(b.GALLERY_TEXT_USAGE):
-        b.build_gallery_text(force=True, verbose=False)
-    usage = json.load(open(b.GALLERY_TEXT_USAGE))
+    if not os.path.exists(b.SIDE_LIBS["gallery_text"].usage):
+        b.build_side("gallery_text", force=True, verbose=False)
+    usage = json.load(open(b.SIDE_LIBS["gallery_text"].usage))
     names = sorted(usage)
     for k in ("frame_mean_kernel", "text_logits_kernel", "text_softmax_kernel", "text_combine_kernel"):
         assert sum(k in n for n in names) == 1, (k, names)
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0, (n, u)
         assert "otam_gallery_kernel" not in n, n
-    assert b.GALLERY_TEXT_SOURCE not in b.SOURCES
-    assert len({b.GALLERY_TEXT_USAGE, b.GALLERY_USAGE, b.USAGE}) == 3
-    for other in (b.USAGE, b.GALLERY_USAGE):
+    assert b.SIDE_LIBS["gallery_text"].source not in b.SOURCES
+    assert len({b.SIDE_LIBS["gallery_text"].usage, b.SIDE_LIBS["gallery"].usage, b.USAGE}) == 3
+    for other in (b.USAGE, b.SIDE_LIBS["gallery"].usage):
         if os.path.exists(other):
             assert not set(usage) & set(json.load(open(other)))
 
 
 def test_product_staleness_ignores_the_text_gallery_source(monkeypatch):
-    """editing csrc/gallery_text.hip rebuilds the text library only: libclipfsar_hip.so's staleness check skips it"""
+    """editing csrc/gallery_text.hip rebuilds the text library only: libclipfsar_hip.so's staleness check skips it; a shared header
+    rebuilds exactly the libraries whose sources include it"""
     from clip_fsar_amd import build as b
+    g, t = b.SIDE_LIBS["gallery"], b.SIDE_LIBS["gallery_text"]
+
+    def stale_after_editing(name):               # (product, gallery, text gallery) with csrc/<name> newer than every library
+        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
+        return b._stale(b.LIB, b._product_deps()), b._stale(g.lib, b._side_deps("gallery")), b._stale(t.lib, b._side_deps("gallery_text"))
+
     monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(b.GALLERY_TEXT_SOURCE) else 1.0)
-    assert not b._stale() and not b._gallery_stale()
-    assert b._side_stale(b.GALLERY_TEXT_LIB, b.GALLERY_TEXT_SOURCE, b.GALLERY_TEXT_HEADER)
+    assert stale_after_editing(t.source) == (False, False, True)
+    assert stale_after_editing(g.source) == (False, True, False)
+    assert stale_after_editing("fp32_tile_gemm.h") == (False, True, True)
+    assert stale_after_editing("side_lib.h") == (False, True, True)
+    assert stale_after_editing("otam_dp.h") == (True, True, False)
+    assert stale_after_editing("common.h") == (True, True, True)
+    assert stale_after_editing("tail.hip") == (True, False, False)
+    assert stale_after_editing("clipfsar_gallery_text.h") == (False, False, True)
 
 
 # ------------------------------------------------------------------ mode resolution (no GPU: a stub head)

@@ -13,7 +13,6 @@
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -22,21 +21,9 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from _timing import _time_ms  # noqa: E402  (tools/_timing.py)
+
 PEAK_F32_MFMA_TF = 157.3          # MI355X: f32-input MFMA = the f32 vector peak (64 FLOP / clk / SIMD)
-
-
-def _time_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        fn()
-        e.record()
-        torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e))
-    return statistics.median(ts)
 
 
 def kernel_point(NQ, C, T, E, reps):
