@@ -35,13 +35,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
-# The side libraries: the support gallery (include/clipfsar_gallery.h) and its text half, the EVAL_TEXT / COMBINE kernels
-# (include/clipfsar_gallery_text.h).  Each is ONE source compiled with the product FLAGS and the fence into a library of its own beside
-# libclipfsar_hip.so (the three pinned export sets stay apart), with its own staleness check and its own resource report
-# (build/resource_usage.json stays the product library's).
+# The side libraries: the support gallery (include/clipfsar_gallery.h), its text half, the EVAL_TEXT / COMBINE kernels
+# (include/clipfsar_gallery_text.h), and the window streams' ring, gather and smoothing kernels (include/clipfsar_stream.h).  Each is ONE
+# source compiled with the product FLAGS and the fence into a library of its own beside libclipfsar_hip.so (the pinned export sets stay
+# apart), with its own staleness check and its own resource report (build/resource_usage.json stays the product library's).
 SideLib = collections.namedtuple("SideLib", "source lib usage")        # the C header (include/clipfsar_<name>.h) is a dependency through #include
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                           os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("gallery", "gallery_text")}
+                           os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("gallery", "gallery_text", "stream")}
 
 
 def _parse_usage(text: str) -> dict:

@@ -1,4 +1,6 @@
 """Support gallery: register classes once from a few example videos each, then classify any stream of query videos against all of them.
+(Whole T-frame clips, that is; for the overlapping windows of a continuous frame stream see clip_fsar_amd.stream.WindowStream, which runs
+the tower once per frame and scores the windows through classify_features.)
 
 In the reference's eval branch (few_shot.py:2944-2990) queries and supports meet only in cos_sim and OTAM: a query goes through context2
 alone (:2948), a support sequence is its T frame features plus its class's text token and goes through context2 without any query
@@ -9,6 +11,7 @@ work is paid once, at registration.
     g = SupportGallery(head, device)             # a CNN_OTAM_CLIPFSAR head (or build_model(cfg)[0].head)
     g.add_classes(videos, class_of_video)        # videos [Nv, T, 3, H, W] fp32 on the device; ids index TEST.CLASS_NAME
     logits = g.classify(queries)                 # [NQ, T, 3, H, W] -> [NQ, C] fp32, columns in registration order
+    logits = g.classify_features(feats)          # [N, T, E] tower features (a cache, a WindowStream's ring) -> the same [N, C]
     values, index = g.topk(queries, k=5)
 
 Every arithmetic step runs on the HIP kernels: the engine's tower (HipViT / HipResNet) and context2 (libclipfsar_hip.so), the support
@@ -213,6 +216,39 @@ class _GalleryBase:
             self._qws[n] = ws
         return ws
 
+    def _check_feats(self, feats):
+        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+            raise RuntimeError("%s: feats must be a HIP device tensor (no CPU path exists)" % self._name)
+        if feats.dim() != 3 or feats.shape[1] != self.T or feats.shape[2] != self.E:
+            raise ValueError("%s: feats must be [N, T=%d, E=%d], got %s" % (self._name, self.T, self.E, tuple(feats.shape)))
+        return feats.to(dtype=torch.float32).contiguous()
+
+    def _scratch(self, nmax, C):
+        """per-call buffers of _score for chunks of at most nmax clips"""
+        return None
+
+    def _classify(self, src, tower):
+        """classify (tower=True: src = the clips' pixels, the tower runs chunk by chunk) and classify_features (src = their tower features):
+        one loop, so both score a chunk with the same launches.  The subclass's _score(eng, feats [n, T, E], n, ws, out [n, C], scratch)
+        holds its eval branch."""
+        eng = self._fresh_engine()
+        if not self._ids:
+            raise RuntimeError("%s: no classes registered" % self._name)
+        src = self._check_videos(src, "queries") if tower else self._check_feats(src)
+        N, C = src.shape[0], len(self._ids)
+        out = torch.empty(N, C, device=self.dev, dtype=torch.float32)
+        chunk = max(1, eng.max_frames // self.T)
+        scratch = self._scratch(min(N, chunk), C)
+        for q0 in range(0, N, chunk):
+            q1 = min(N, q0 + chunk)
+            ws = self._query_ws(q1 - q0)
+            feats = src[q0:q1]
+            if tower:
+                feats = ws["feats"]
+                self._features(eng, src[q0:q1], feats)
+            self._score(eng, feats, q1 - q0, ws, out[q0:q1], scratch)
+        return out
+
     def topk(self, queries, k=5):
         """(values [NQ, k] fp32 descending, class index [NQ, k] int32 into class_ids); ties go to the lower index"""
         if not 1 <= k <= min(ghip.TOPK_MAX, max(1, len(self._ids))):
@@ -280,21 +316,16 @@ class SupportGallery(_GalleryBase):
 
     def classify(self, queries):
         """queries [NQ, T, 3, H, W] fp32 (device) -> logits [NQ, C] fp32 = -(OTAM + OTAM^T) against every registered class, in registration order"""
-        eng = self._fresh_engine()
-        if not self._ids:
-            raise RuntimeError("SupportGallery: no classes registered")
-        queries = self._check_videos(queries, "queries")
-        NQ, T, C = queries.shape[0], self.T, len(self._ids)
-        logits = torch.empty(NQ, C, device=self.dev, dtype=torch.float32)
-        chunk = max(1, eng.max_frames // T)
-        for q0 in range(0, NQ, chunk):
-            q1 = min(NQ, q0 + chunk)
-            n = q1 - q0
-            ws = self._query_ws(n)
-            self._features(eng, queries[q0:q1], ws["feats"])
-            Xq = self._context2(eng, ws["feats"], n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
-            # the gallery kernel at every class count: faster than the episode kernel (cfsar_cos_otam_logits) from C = 5 on
-            # (1.7 x at 1 024 queries x 5 classes, 4.9 x at 24, 11.5 x at 1 024; profiles/gallery_time.json)
-            ghip.row_norms(Xq, ws["qn"])
-            ghip.otam_gallery(Xq, ws["qn"], self._P, self._pn, logits[q0:q1], LAMBDA, self.single_direct)
-        return logits
+        return self._classify(queries, tower=True)
+
+    def classify_features(self, feats):
+        """feats [N, T, E] fp32 (device), the tower features of N clips -> the logits [N, C] classify gives for those clips"""
+        return self._classify(feats, tower=False)
+
+    def _score(self, eng, feats, n, ws, out, scratch):
+        T = self.T
+        Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
+        # the gallery kernel at every class count: faster than the episode kernel (cfsar_cos_otam_logits) from C = 5 on
+        # (1.7 x at 1 024 queries x 5 classes, 4.9 x at 24, 11.5 x at 1 024; profiles/gallery_time.json)
+        ghip.row_norms(Xq, ws["qn"])
+        ghip.otam_gallery(Xq, ws["qn"], self._P, self._pn, out, LAMBDA, self.single_direct)

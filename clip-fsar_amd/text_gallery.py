@@ -4,6 +4,7 @@
     g.add_text_classes([3, 7, "kite"], text={"kite": row_or_name})   # EVAL_TEXT only: zero-shot classes from their text alone
     g.add_classes(videos, class_of_video)         # as SupportGallery.add_classes; COMBINE builds the visual prototypes
     probs = g.classify(queries)                   # [NQ, T, 3, H, W] -> [NQ, C] fp32, columns in registration order
+    probs = g.classify_features(feats)            # [N, T, E] tower features -> the same [N, C] (clip_fsar_amd.stream.WindowStream)
     values, index = g.topk(queries, k=5)
 
 EVAL_TEXT (few_shot.py:2835-2852): softmax over the classes of scale * cos(mean_T of the query's tower features, the class's text row).
@@ -140,32 +141,29 @@ class TextGallery(_GalleryBase):
     def classify(self, queries):
         """queries [NQ, T, 3, H, W] fp32 (device) -> [NQ, C] fp32 against every registered class, in registration order: the text
         probabilities (EVAL_TEXT) or their fusion with the OTAM logits (COMBINE)"""
-        eng = self._fresh_engine()
-        if not self._ids:
-            raise RuntimeError("TextGallery: no classes registered")
-        queries = self._check_videos(queries, "queries")
-        NQ, T, E, C = queries.shape[0], self.T, self.E, len(self._ids)
-        out = torch.empty(NQ, C, device=self.dev, dtype=torch.float32)
-        chunk = max(1, eng.max_frames // T)
-        nmax = min(NQ, chunk)
+        return self._classify(queries, tower=True)
+
+    def classify_features(self, feats):
+        """feats [N, T, E] fp32 (device), the tower features of N clips -> what classify gives for those clips [N, C]"""
+        return self._classify(feats, tower=False)
+
+    def _scratch(self, nmax, C):
         partials = torch.empty(gt.workspace_floats(nmax, C), device=self.dev, dtype=torch.float32)
         vis = torch.empty(nmax, C, device=self.dev, dtype=torch.float32) if self.mode == "combine" else None
-        for q0 in range(0, NQ, chunk):
-            q1 = min(NQ, q0 + chunk)
-            n = q1 - q0
-            ws = self._query_ws(n)
-            if "emb" not in ws:
-                ws.update(emb=torch.empty(n, E, device=self.dev, dtype=torch.float32), en=torch.empty(n, device=self.dev, dtype=torch.float32))
-            self._features(eng, queries[q0:q1], ws["feats"])          # the tower runs once per query; both halves read its output
-            o = out[q0:q1]
-            gt.frame_mean(ws["feats"], ws["emb"])                       # :2838-2841 (tower features, not context2's)
-            ghip.row_norms(ws["emb"], ws["en"])
-            gt.text_logits(ws["emb"], ws["en"], self._text, self._tn, eng.scale, o, partials)
-            if self.mode == "eval_text":
-                gt.text_softmax(o, partials, o)
-                continue
-            Xq = self._context2(eng, ws["feats"], n, T, n_a_form=True)[:n * T].view(n, T, E)        # :2948
-            ghip.row_norms(Xq, ws["qn"])
-            ghip.otam_gallery(Xq, ws["qn"], self._P, self._pn, vis[:n], LAMBDA, self.single_direct)
-            gt.text_combine(o, partials, vis[:n], o, self.text_coff)
-        return out
+        return partials, vis
+
+    def _score(self, eng, feats, n, ws, o, scratch):
+        T, E = self.T, self.E
+        partials, vis = scratch
+        if "emb" not in ws:
+            ws.update(emb=torch.empty(n, E, device=self.dev, dtype=torch.float32), en=torch.empty(n, device=self.dev, dtype=torch.float32))
+        gt.frame_mean(feats, ws["emb"])                             # :2838-2841 (tower features, not context2's); both halves read them
+        ghip.row_norms(ws["emb"], ws["en"])
+        gt.text_logits(ws["emb"], ws["en"], self._text, self._tn, eng.scale, o, partials)
+        if self.mode == "eval_text":
+            gt.text_softmax(o, partials, o)
+            return
+        Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, E)        # :2948
+        ghip.row_norms(Xq, ws["qn"])
+        ghip.otam_gallery(Xq, ws["qn"], self._P, self._pn, vis[:n], LAMBDA, self.single_direct)
+        gt.text_combine(o, partials, vis[:n], o, self.text_coff)
