@@ -1,0 +1,294 @@
+"""Stream pool: window streams that join, leave and push unevenly, classified together against a gallery.
+
+    p = StreamPool(gallery, max_streams=64, stride=2, rate=1, max_push=64, smooth=0.0)   # gallery: SupportGallery or TextGallery
+    a, b = p.open(), p.open()              # session handles: ints, never reused; a slot of the ring is reused after close()
+    out = p.push({a: fa, b: fb})           # fa [na, 3, H, W], fb [nb, 3, H, W] fp32 on the device; any subset of the open sessions, n >= 1 each
+    out[a].first_window, out[a].logits     # a StreamOutput per session: [nWa, C] fp32 (nWa may be 0); .smoothed or None
+    po = p.push_packed(frames, sessions=[a, b], counts=[na, nb])    # frames [na + nb, 3, H, W]: the primitive the dict form calls
+    po.sessions, po.first_window, po.offsets, po.logits             # logits [sum nW, C], session-major in the order given, windows ascending
+    p.push_features({a: feats_a}); p.push_features_packed(feats, sessions, counts)          # [n, E] tower features computed elsewhere
+    values, index = p.topk(po, k=5)
+    p.reset(a); p.close(a); p.stats(a); p.stats()
+
+clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
+at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
+that delivers its last frame (stream.window_plan per session).  The tower is per frame and a window's scores depend on its own T frames
+alone, so the frames of unrelated sessions share one tower call sequence and their windows share context2 and the gallery launch: a
+window's logits are what gallery.classify returns for its clip, in the gallery's own mode.
+
+A push is described to the device by one descriptor table with a row per session (libclipfsar_pool.so, clip_fsar_amd.pool_hip): one ring
+write per round, one gather plus one classify_features per chunk of windows, whatever the number of sessions.  A session's push beyond
+max_push frames is split into rounds (round r takes up to max_push of what each session has left).  Sessions absent from a push are
+untouched.  Smoothing state is per session: y_0 = x_0, y_k = fmaf(alpha, y_{k-1}, (1 - alpha) * x_k), the bits of WindowStream's.
+"""
+from __future__ import annotations
+
+import collections
+import heapq
+
+import torch
+
+from . import gallery_hip as ghip
+from . import pool_hip as php
+from .gallery import _GalleryBase
+from .stream import StreamOutput, window_plan
+
+PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
+# One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
+# position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
+Round = collections.namedtuple("Round", "rows members src")
+Plan = collections.namedtuple("Plan", "rounds first_window n_windows order")
+
+
+def plan_push(sessions, counts, T, stride, rate, max_push, smoothing=False):
+    """The host plan of one push.  sessions: (ring slot, frames pushed so far) per session, counts: frames each pushes now.
+    -> Plan(rounds, first_window and n_windows per session, order).  The windows come off the device round-major (every round
+    session-major); order[i] is the position there of row i of the session-major result, or None when the two orders agree."""
+    cap = (T - 1) * rate + max_push
+    first_window = [window_plan(t, 0, T, stride, rate)[0] for _, t in sessions]
+    starts = [0]
+    for n in counts:
+        starts.append(starts[-1] + n)
+    rounds, done, where = [], [0] * len(sessions), [[] for _ in sessions]
+    emitted = 0
+    while any(d < n for d, n in zip(done, counts)):
+        rows, members, src = [], [], []
+        feat_off = win_off = 0
+        for i, ((slot, t0), total) in enumerate(zip(sessions, counts)):
+            n = min(max_push, total - done[i])
+            if n <= 0:
+                continue
+            t = t0 + done[i]
+            first, nW = window_plan(t, n, T, stride, rate)
+            rows.append([slot, t % cap, n, feat_off, (first * stride) % cap, nW, win_off, int(bool(smoothing) and first > 0)])
+            members.append(i)
+            src.append((starts[i] + done[i], n))
+            where[i].extend(range(emitted + win_off, emitted + win_off + nW))
+            feat_off, win_off = feat_off + n, win_off + nW
+            done[i] += n
+        emitted += win_off
+        rounds.append(Round(rows, members, src))
+    order = [g for w in where for g in w]
+    return Plan(rounds, first_window, [len(w) for w in where], None if order == list(range(len(order))) else order)
+
+
+class _Session:
+    __slots__ = ("slot", "t", "tower_frames", "state_gen")
+
+    def __init__(self, slot):
+        self.slot = slot
+        self.clear()
+
+    def clear(self):
+        self.t = 0                               # frames pushed since open() / reset()
+        self.tower_frames = 0
+        self.state_gen = None                    # generation of the pool's smoothing buffer this session's state row was written in
+
+
+class StreamPool:
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0):
+        if not isinstance(gallery, _GalleryBase):
+            raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
+        for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError("StreamPool: %s must be an integer >= 1, got %r" % (name, v))
+        if max_streams > php.MAX_STREAMS:
+            raise ValueError("StreamPool: max_streams = %d, the pool library serves at most %d" % (max_streams, php.MAX_STREAMS))
+        smooth = float(smooth)
+        if not 0.0 <= smooth < 1.0:
+            raise ValueError("StreamPool: smooth must be in [0, 1), got %r" % smooth)
+        if gallery.T > php.MAX_T:
+            raise ValueError("StreamPool: T = %d frames per window, the pool library gathers at most %d" % (gallery.T, php.MAX_T))
+        self.gallery = gallery
+        self.dev = gallery.dev
+        self.max_streams, self.stride, self.rate, self.max_push, self.alpha = max_streams, stride, rate, max_push, smooth
+        self.T, self.E = gallery.T, gallery.E
+        self.cap = (self.T - 1) * rate + max_push
+        self._ring = torch.empty(max_streams, self.cap, self.E, device=self.dev, dtype=torch.float32)
+        self._X = None                           # gathered windows [rows, T, E], grown on demand
+        self._state = None                       # smoothing state [max_streams, C], indexed by slot
+        self._state_gen = 0                      # bumped whenever _state is allocated anew (the class count changed)
+        self._tables = php.TableUploader(self.dev, max_streams)
+        self._sessions = {}                      # handle -> _Session
+        self._free = list(range(max_streams))    # a heap: the lowest free slot is taken first
+        self._next_handle = 0
+        self._totals = {"frames": 0, "tower_frames": 0, "windows": 0}
+
+    # ------------------------------------------------------------------ sessions
+    def open(self):
+        """a new session, its frames numbered from 0 -> its handle"""
+        if not self._free:
+            raise RuntimeError("StreamPool: all %d slots are in use -- close() a session or build the pool with a larger max_streams"
+                               % self.max_streams)
+        h = self._next_handle
+        self._next_handle += 1
+        self._sessions[h] = _Session(heapq.heappop(self._free))
+        return h
+
+    def _session(self, h):
+        s = self._sessions.get(h) if isinstance(h, int) and not isinstance(h, bool) else None
+        if s is None:
+            raise ValueError("StreamPool: session %r is not open (closed, or never returned by open())" % (h,))
+        return s
+
+    def close(self, h):
+        """the session's slot becomes free; its handle is never valid again"""
+        heapq.heappush(self._free, self._session(h).slot)
+        del self._sessions[h]
+
+    def reset(self, h):
+        """Frame counter 0; the session's ring contents and smoothing state are dropped."""
+        self._session(h).clear()
+
+    @property
+    def sessions(self):
+        return sorted(self._sessions)
+
+    def stats(self, h=None):
+        """of a session: frames, tower_frames and windows since open() / reset(); of the pool: what all pushes added up to, and the open sessions"""
+        if h is None:
+            return dict(self._totals, open=len(self._sessions))
+        s = self._session(h)
+        return {"frames": s.t, "tower_frames": s.tower_frames, "windows": window_plan(0, s.t, self.T, self.stride, self.rate)[1]}
+
+    # ------------------------------------------------------------------ pushes
+    def _ready(self):
+        g = self.gallery
+        eng = g._fresh_engine()
+        if not len(g):
+            raise RuntimeError("%s: no classes registered" % g._name)
+        return eng
+
+    def _check(self, t, tail, what, layout, sessions, counts):
+        """-> (the packed tensor as fp32, the sessions' records, counts as ints); every error of a push is raised here, before any launch"""
+        sessions = list(sessions)
+        counts = [int(c) for c in counts]
+        recs = [self._session(h) for h in sessions]
+        if len(set(sessions)) != len(sessions):
+            raise ValueError("StreamPool: a session appears twice in one push: %r" % (sessions,))
+        if not sessions or len(counts) != len(sessions) or min(counts) < 1:
+            raise ValueError("StreamPool: a push needs sessions and one count >= 1 for each, got %d sessions, counts %r" % (
+                len(sessions), counts))
+        if isinstance(t, torch.Tensor) and t.dim() and sum(counts) != t.shape[0]:
+            raise ValueError("StreamPool: counts sum to %d, %s holds %d frames" % (sum(counts), what, t.shape[0]))
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("StreamPool: %s must be a HIP device tensor (no CPU path exists)" % what)
+        if t.dim() != 1 + len(tail) or any(want is not None and got != want for got, want in zip(t.shape[1:], tail)):
+            raise ValueError("StreamPool: %s must be %s, got %s" % (what, layout, tuple(t.shape)))
+        if self.alpha:
+            C = len(self.gallery)
+            fresh = self._state is None or self._state.shape[1] != C
+            for h, s in zip(sessions, recs):
+                if s.state_gen is not None and (fresh or s.state_gen != self._state_gen):
+                    raise RuntimeError("StreamPool: the gallery has %d classes, the smoothing state of session %d was made with another "
+                                       "count -- reset() the session after adding classes when smoothing is on" % (C, h))
+        return t.to(dtype=torch.float32).contiguous(), recs, counts
+
+    def push_packed(self, frames, sessions, counts):
+        """frames [N, 3, H, W] fp32 (device): counts[i] next frames of sessions[i], one session after the other -> PackedOutput of the
+        windows they complete.  The tower runs once per frame, in one call sequence over all of them."""
+        eng = self._ready()
+        frames, recs, counts = self._check(frames, (3, None, None), "frames", "[N, 3, H, W]", sessions, counts)
+        feats = torch.empty(frames.shape[0], self.E, device=self.dev, dtype=torch.float32)
+        for f0 in range(0, frames.shape[0], eng.max_frames):
+            f1 = min(frames.shape[0], f0 + eng.max_frames)
+            eng.vit.forward(frames[f0:f1], feats[f0:f1])
+        for s, n in zip(recs, counts):
+            s.tower_frames += n
+        self._totals["tower_frames"] += frames.shape[0]
+        return self._run(eng, feats, list(sessions), recs, counts)
+
+    def push_features_packed(self, feats, sessions, counts):
+        """feats [N, E] fp32 (device): the tower features of the frames -> as push_packed"""
+        eng = self._ready()
+        feats, recs, counts = self._check(feats, (self.E,), "feats", "[N, E=%d]" % self.E, sessions, counts)
+        return self._run(eng, feats, list(sessions), recs, counts)
+
+    def _by_session(self, packed_call, per_session, what, dims):
+        self._ready()
+        if not isinstance(per_session, dict) or not per_session:
+            raise ValueError("StreamPool: a push takes a non-empty dict {session: %s}" % what)
+        for h, t in per_session.items():
+            self._session(h)
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError("StreamPool: %s of session %r must be a HIP device tensor (no CPU path exists)" % (what, h))
+            if t.dim() != dims or t.shape[0] < 1:
+                raise ValueError("StreamPool: %s of session %r must have %d dimensions and n >= 1 rows, got %s" % (
+                    what, h, dims, tuple(t.shape)))
+        ts = list(per_session.values())
+        po = packed_call(ts[0] if len(ts) == 1 else torch.cat(ts, 0), list(per_session), [t.shape[0] for t in ts])
+        out = {}
+        for i, h in enumerate(po.sessions):
+            w0, w1 = po.offsets[i], po.offsets[i + 1]
+            out[h] = StreamOutput(po.first_window[i], po.logits[w0:w1], None if po.smoothed is None else po.smoothed[w0:w1])
+        return out
+
+    def push(self, frames):
+        """{session: frames [n, 3, H, W]} -> {session: StreamOutput}; one push_packed over all of them"""
+        return self._by_session(self.push_packed, frames, "frames", 4)
+
+    def push_features(self, feats):
+        """{session: feats [n, E]} -> {session: StreamOutput}; one push_features_packed over all of them"""
+        return self._by_session(self.push_features_packed, feats, "feats", 2)
+
+    def _run(self, eng, feats, handles, recs, counts):
+        g, T, C = self.gallery, self.T, len(self.gallery)
+        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push, smoothing=bool(self.alpha))
+        NW = sum(plan.n_windows)
+        logits = torch.empty(NW, C, device=self.dev, dtype=torch.float32)
+        smoothed = torch.empty_like(logits) if self.alpha else None
+        if self.alpha and NW and (self._state is None or self._state.shape[1] != C):
+            self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
+            self._state_gen += 1
+        per = max(1, eng.max_frames // T)        # classify_features scores that many clips per chunk: gather no more at a time
+        g0 = 0
+        for rnd in plan.rounds:
+            if len(plan.rounds) == 1:
+                piece = feats
+            else:                                # a later round's frames lie apart in the packed features: pack them for the ring write
+                piece = torch.cat([feats[f0:f0 + n] for f0, n in rnd.src], 0)
+            table = self._tables.upload(rnd.rows)
+            php.ring_put(piece, self._ring, table)
+            nW = sum(r[php.NW] for r in rnd.rows)
+            if nW == 0:
+                continue
+            if self._X is None or self._X.shape[0] < min(nW, per):
+                self._X = torch.empty(min(nW, per), T, self.E, device=self.dev, dtype=torch.float32)
+            out = logits[g0:g0 + nW]
+            for w0 in range(0, nW, per):
+                w1 = min(nW, w0 + per)
+                X = self._X[:w1 - w0]
+                php.window_sequences(self._ring, X, table, nW, w0, w1, T, self.stride, self.rate)
+                out[w0:w1].copy_(g.classify_features(X))
+            if self.alpha:
+                php.smooth_logits(out, self._state, smoothed[g0:g0 + nW], table, self.alpha)
+            g0 += nW
+        if plan.order is not None and NW:        # several rounds: round-major -> session-major
+            index = torch.tensor(plan.order, device=self.dev)
+            logits = logits.index_select(0, index)
+            smoothed = smoothed.index_select(0, index) if self.alpha else None
+        offsets = [0]
+        for s, n, nW in zip(recs, counts, plan.n_windows):
+            s.t += n
+            if self.alpha and nW:
+                s.state_gen = self._state_gen
+            offsets.append(offsets[-1] + nW)
+        self._totals["frames"] += sum(counts)
+        self._totals["windows"] += NW
+        return PackedOutput(handles, plan.first_window, offsets, logits, smoothed)
+
+    # ------------------------------------------------------------------ top-k
+    def topk(self, out, k=5, smoothed=False):
+        """(values [nW, k] fp32 descending, class index [nW, k] int32 into gallery.class_ids) of every window of a PackedOutput or a
+        StreamOutput (of out.smoothed with smoothed=True); ties go to the lower index"""
+        src = out.smoothed if smoothed else out.logits
+        if src is None:
+            raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")
+        nW, C = src.shape
+        if not 1 <= k <= min(ghip.TOPK_MAX, max(1, C)):
+            raise ValueError("StreamPool.topk: k must be in [1, min(16, number of classes)], got %d" % k)
+        values = torch.empty(nW, k, device=src.device, dtype=torch.float32)
+        index = torch.empty(nW, k, device=src.device, dtype=torch.int32)
+        if nW:
+            ghip.topk(src.contiguous(), k, values, index)
+        return values, index
