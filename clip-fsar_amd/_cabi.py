@@ -1,4 +1,4 @@
-"""What the five ctypes bindings (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip) share: loading a C-ABI library against its signature table, and the
+"""What the six ctypes bindings (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip) share: loading a C-ABI library against its signature table, and the
 builders of their ``_check`` / ``_shape`` helpers.  Each binding keeps its own SIGNATURES, ABI_VERSION, LIB_PATH and ``lib()``."""
 from __future__ import annotations
 

@@ -1,5 +1,6 @@
 // Memory-bound row kernels of the ViT tower: patch gather (im2col), class-token rows, LayerNorm.
 #include "common.h"
+#include "frame_transform.h"
 
 namespace {
 
@@ -123,34 +124,18 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
                                                          int H, int W, int sh, int sw, int crop, int y0, int x0, float m0,
                                                          float m1, float m2, float is0, float is1, float is2) {
     const long long total = (long long)T * crop * crop;
-    const float ry = (float)H / (float)sh, rx = (float)W / (float)sw;       // torch: scale = in / out
+    const float ry = frame_transform_ratio(H, sh), rx = frame_transform_ratio(W, sw);
+    const float mean[3] = {m0, m1, m2}, istd[3] = {is0, is1, is2};
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(idx % crop);
         const long long r = idx / crop;
         const int y = (int)(r % crop);
         const int t = (int)(r / crop);
-        float fy = ry * ((float)(y + y0) + 0.5f) - 0.5f;                     // area_pixel_compute_source_index
-        float fx = rx * ((float)(x + x0) + 0.5f) - 0.5f;
-        fy = fy < 0.f ? 0.f : fy;
-        fx = fx < 0.f ? 0.f : fx;
-        const int iy0 = (int)fy, ix0 = (int)fx;
-        const int iy1 = iy0 + (iy0 < H - 1 ? 1 : 0), ix1 = ix0 + (ix0 < W - 1 ? 1 : 0);
-        const float ly = fy - (float)iy0, lx = fx - (float)ix0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        const unsigned char* f = src + (long long)t * H * W * 3;
-        const unsigned char* p00 = f + ((long long)iy0 * W + ix0) * 3;
-        const unsigned char* p01 = f + ((long long)iy0 * W + ix1) * 3;
-        const unsigned char* p10 = f + ((long long)iy1 * W + ix0) * 3;
-        const unsigned char* p11 = f + ((long long)iy1 * W + ix1) * 3;
-        const float mean[3] = {m0, m1, m2}, istd[3] = {is0, is1, is2};
+        float v[3];
+        frame_transform_pixel(src + (long long)t * H * W * 3, H, W, ry, rx, y + y0, x + x0, mean, istd, v);      // frame_transform.h
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float inv255 = 1.0f / 255.0f;
-            const float v = hy * (hx * ((float)p00[c] * inv255) + lx * ((float)p01[c] * inv255)) +
-                            ly * (hx * ((float)p10[c] * inv255) + lx * ((float)p11[c] * inv255));
-            out[(((long long)t * 3 + c) * crop + y) * crop + x] = (v - mean[c]) * istd[c];
-        }
+        for (int c = 0; c < 3; ++c) out[(((long long)t * 3 + c) * crop + y) * crop + x] = v[c];
     }
 }
 

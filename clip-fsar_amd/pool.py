@@ -7,6 +7,8 @@
     po = p.push_packed(frames, sessions=[a, b], counts=[na, nb])    # frames [na + nb, 3, H, W]: the primitive the dict form calls
     po.sessions, po.first_window, po.offsets, po.logits             # logits [sum nW, C], session-major in the order given, windows ascending
     p.push_features({a: feats_a}); p.push_features_packed(feats, sessions, counts)          # [n, E] tower features computed elsewhere
+    p.push_u8({a: ua, b: ub}); p.push_u8_packed([ua, ub], [a, b])     # decoded uint8 [n, H, W, 3] clips, each of its own H x W, on the host
+                                                                      # or the device: clip_fsar_amd.ingest.FrameIngest, then push_packed
     values, index = p.topk(po, k=5)
     p.reset(a); p.close(a); p.stats(a); p.stats()
 
@@ -31,6 +33,7 @@ import torch
 from . import gallery_hip as ghip
 from . import pool_hip as php
 from .gallery import _GalleryBase
+from .ingest import FrameIngest
 from .stream import StreamOutput, window_plan
 
 PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
@@ -86,7 +89,7 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0):
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None):
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -113,6 +116,11 @@ class StreamPool:
         self._free = list(range(max_streams))    # a heap: the lowest free slot is taken first
         self._next_handle = 0
         self._totals = {"frames": 0, "tower_frames": 0, "windows": 0}
+        if ingest is not None and not isinstance(ingest, FrameIngest):
+            raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
+        if ingest is not None:
+            ingest.serves(self.dev, who="StreamPool")
+        self._ingest = ingest                    # push_u8's transform; None: built from gallery.head.args by the first push_u8
 
     # ------------------------------------------------------------------ sessions
     def open(self):
@@ -161,6 +169,18 @@ class StreamPool:
 
     def _check(self, t, tail, what, layout, sessions, counts):
         """-> (the packed tensor as fp32, the sessions' records, counts as ints); every error of a push is raised here, before any launch"""
+        recs, counts = self._check_members(sessions, counts)
+        if isinstance(t, torch.Tensor) and t.dim() and sum(counts) != t.shape[0]:
+            raise ValueError("StreamPool: counts sum to %d, %s holds %d frames" % (sum(counts), what, t.shape[0]))
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("StreamPool: %s must be a HIP device tensor (no CPU path exists)" % what)
+        if t.dim() != 1 + len(tail) or any(want is not None and got != want for got, want in zip(t.shape[1:], tail)):
+            raise ValueError("StreamPool: %s must be %s, got %s" % (what, layout, tuple(t.shape)))
+        self._check_state(sessions, recs)
+        return t.to(dtype=torch.float32).contiguous(), recs, counts
+
+    def _check_members(self, sessions, counts):
+        """-> (the sessions' records, counts as ints): open sessions, each once, a count >= 1 for each"""
         sessions = list(sessions)
         counts = [int(c) for c in counts]
         recs = [self._session(h) for h in sessions]
@@ -169,12 +189,9 @@ class StreamPool:
         if not sessions or len(counts) != len(sessions) or min(counts) < 1:
             raise ValueError("StreamPool: a push needs sessions and one count >= 1 for each, got %d sessions, counts %r" % (
                 len(sessions), counts))
-        if isinstance(t, torch.Tensor) and t.dim() and sum(counts) != t.shape[0]:
-            raise ValueError("StreamPool: counts sum to %d, %s holds %d frames" % (sum(counts), what, t.shape[0]))
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("StreamPool: %s must be a HIP device tensor (no CPU path exists)" % what)
-        if t.dim() != 1 + len(tail) or any(want is not None and got != want for got, want in zip(t.shape[1:], tail)):
-            raise ValueError("StreamPool: %s must be %s, got %s" % (what, layout, tuple(t.shape)))
+        return recs, counts
+
+    def _check_state(self, sessions, recs):
         if self.alpha:
             C = len(self.gallery)
             fresh = self._state is None or self._state.shape[1] != C
@@ -182,7 +199,6 @@ class StreamPool:
                 if s.state_gen is not None and (fresh or s.state_gen != self._state_gen):
                     raise RuntimeError("StreamPool: the gallery has %d classes, the smoothing state of session %d was made with another "
                                        "count -- reset() the session after adding classes when smoothing is on" % (C, h))
-        return t.to(dtype=torch.float32).contiguous(), recs, counts
 
     def push_packed(self, frames, sessions, counts):
         """frames [N, 3, H, W] fp32 (device): counts[i] next frames of sessions[i], one session after the other -> PackedOutput of the
@@ -216,7 +232,11 @@ class StreamPool:
                 raise ValueError("StreamPool: %s of session %r must have %d dimensions and n >= 1 rows, got %s" % (
                     what, h, dims, tuple(t.shape)))
         ts = list(per_session.values())
-        po = packed_call(ts[0] if len(ts) == 1 else torch.cat(ts, 0), list(per_session), [t.shape[0] for t in ts])
+        return self._split(packed_call(ts[0] if len(ts) == 1 else torch.cat(ts, 0), list(per_session), [t.shape[0] for t in ts]))
+
+    @staticmethod
+    def _split(po):
+        """PackedOutput -> {session: StreamOutput}"""
         out = {}
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
@@ -230,6 +250,38 @@ class StreamPool:
     def push_features(self, feats):
         """{session: feats [n, E]} -> {session: StreamOutput}; one push_features_packed over all of them"""
         return self._by_session(self.push_features_packed, feats, "feats", 2)
+
+    # ------------------------------------------------------------------ pushes of decoded uint8 clips
+    @property
+    def ingest(self):
+        """the FrameIngest of push_u8: the constructor's, or one built here from gallery.head.args (DATA.TEST_SCALE, TEST_CROP_SIZE, MEAN, STD)"""
+        if self._ingest is None:
+            self._ingest = FrameIngest.from_cfg(self.gallery.head.args, self.dev)
+        return self._ingest
+
+    def push_u8_packed(self, clips, sessions):
+        """clips: a list of uint8 [n_i, H_i, W_i, 3], the next frames of sessions[i], each clip of its own geometry and on the device, in
+        pinned or in pageable host memory -> PackedOutput.  FrameIngest.transform (one upload on its copy stream, one launch), then
+        push_packed on its result: the same rounds, tables and stats.  Every error is raised before the upload starts."""
+        eng = self._ready()
+        ingest = self.ingest
+        ingest.serves(self.dev, getattr(eng, "arch", {}).get("res"), "StreamPool")
+        if not isinstance(clips, (list, tuple)) or not clips:
+            raise ValueError("StreamPool: push_u8_packed takes a non-empty list of uint8 [n, H, W, 3] clips")
+        sessions = list(sessions)
+        if len(sessions) != len(clips):
+            raise ValueError("StreamPool: %d clips for %d sessions" % (len(clips), len(sessions)))
+        counts = [n for n, _, _ in ingest.check(clips)]
+        recs, counts = self._check_members(sessions, counts)
+        self._check_state(sessions, recs)
+        return self.push_packed(ingest.transform(clips), sessions, counts)
+
+    def push_u8(self, clips):
+        """{session: uint8 [n, H, W, 3]} -> {session: StreamOutput}; one push_u8_packed over all of them"""
+        self._ready()
+        if not isinstance(clips, dict) or not clips:
+            raise ValueError("StreamPool: a push takes a non-empty dict {session: uint8 [n, H, W, 3] frames}")
+        return self._split(self.push_u8_packed(list(clips.values()), list(clips)))
 
     def _run(self, eng, feats, handles, recs, counts):
         g, T, C = self.gallery, self.T, len(self.gallery)

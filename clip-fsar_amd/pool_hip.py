@@ -56,21 +56,21 @@ Table = collections.namedtuple("Table", "host dev S")          # host: pinned [S
 class TableUploader:
     """upload(rows) -> Table: the rows in a pinned host buffer and their device copy, enqueued on the current stream.  `depth` buffer pairs
     are used in turn; before a pair is rewritten the event recorded after its last copy is waited for (it has long completed unless the
-    host runs `depth` uploads ahead of the device)."""
+    host runs `depth` uploads ahead of the device).  `cols`: values per row (clip_fsar_amd.ingest_hip uploads its own table layout)."""
 
-    def __init__(self, device, max_rows, depth=4):
-        self.dev, self.max_rows, self.depth = torch.device(device), int(max_rows), int(depth)
+    def __init__(self, device, max_rows, depth=4, cols=TABLE_COLS):
+        self.dev, self.max_rows, self.depth, self.cols = torch.device(device), int(max_rows), int(depth), int(cols)
         self._host = self._devbuf = self._events = None
         self._next = 0
 
     def upload(self, rows):
         S = len(rows)
-        if not 1 <= S <= self.max_rows or any(len(r) != TABLE_COLS for r in rows):
+        if not 1 <= S <= self.max_rows or any(len(r) != self.cols for r in rows):
             raise RuntimeError("clip_fsar_amd.pool_hip: a table must have 1 .. %d rows of %d values, got %d rows" % (
-                self.max_rows, TABLE_COLS, S))
+                self.max_rows, self.cols, S))
         if self._host is None:
-            self._host = [torch.empty(self.max_rows, TABLE_COLS, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
-            self._devbuf = torch.empty(self.depth, self.max_rows, TABLE_COLS, dtype=torch.int32, device=self.dev)
+            self._host = [torch.empty(self.max_rows, self.cols, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+            self._devbuf = torch.empty(self.depth, self.max_rows, self.cols, dtype=torch.int32, device=self.dev)
             self._events = [None] * self.depth
         i = self._next
         self._next = (i + 1) % self.depth

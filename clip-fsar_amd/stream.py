@@ -5,6 +5,7 @@
     out.first_window, out.logits       # k of the first window this push completed; [B, nW, C] fp32 (nW may be 0); out.smoothed or None
     values, index = s.topk(out, k=5)
     out = s.push_features(feats)       # feats [B, n, E] fp32: tower features computed elsewhere
+    out = s.push_u8(frames_u8)         # decoded uint8 [B, n, H, W, 3] on the host or the device: clip_fsar_amd.ingest.FrameIngest, then push
     s.reset(); s.stats
 
 In the eval branch the tower is per frame (few_shot.py:971-999, get_feats): nothing mixes frames before context2, so a frame's tower
@@ -28,6 +29,7 @@ import torch
 from . import gallery_hip as ghip
 from . import stream_hip as shp
 from .gallery import _GalleryBase
+from .ingest import FrameIngest
 
 StreamOutput = collections.namedtuple("StreamOutput", "first_window logits smoothed")
 
@@ -48,7 +50,7 @@ def window_plan(frames_before, n, T, stride, rate):
 
 
 class WindowStream:
-    def __init__(self, gallery, n_streams=1, stride=1, rate=1, max_push=64, smooth=0.0):
+    def __init__(self, gallery, n_streams=1, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None):
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("WindowStream: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("n_streams", n_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -66,6 +68,11 @@ class WindowStream:
         self.cap = (self.T - 1) * rate + max_push
         self._ring = torch.empty(self.B, self.cap, self.E, device=self.dev, dtype=torch.float32)
         self._X = None                           # gathered windows [rows, T, E], grown on demand
+        if ingest is not None and not isinstance(ingest, FrameIngest):
+            raise TypeError("WindowStream: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
+        if ingest is not None:
+            ingest.serves(self.dev, who="WindowStream")
+        self._ingest = ingest                    # push_u8's transform; None: built from gallery.head.args by the first push_u8
         self.reset()
 
     def reset(self):
@@ -107,6 +114,27 @@ class WindowStream:
         eng = self._ready()
         feats = self._check(feats, (self.E,), "feats", "[B, n, E=%d]" % self.E)
         return self._pieces(eng, feats, tower=False)
+
+    @property
+    def ingest(self):
+        """the FrameIngest of push_u8: the constructor's, or one built here from gallery.head.args (DATA.TEST_SCALE, TEST_CROP_SIZE, MEAN, STD)"""
+        if self._ingest is None:
+            self._ingest = FrameIngest.from_cfg(self.gallery.head.args, self.dev)
+        return self._ingest
+
+    def push_u8(self, frames):
+        """frames uint8 [B, n, H, W, 3], on the device, in pinned or in pageable host memory: the next n decoded frames of every stream ->
+        as push.  One FrameIngest.transform over all of them (one group), then push on its result; errors are raised before the upload."""
+        eng = self._ready()
+        ingest = self.ingest
+        ingest.serves(self.dev, getattr(eng, "arch", {}).get("res"), "WindowStream")
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 5 or frames.shape[0] != self.B or frames.shape[1] < 1:
+            raise ValueError("WindowStream: frames must be uint8 [B, n, H, W, 3] with B = %d, n >= 1, got %s" % (
+                self.B, tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames).__name__))
+        B, n = frames.shape[:2]
+        clip = frames.reshape(B * n, *frames.shape[2:])
+        ingest.check([clip])
+        return self.push(ingest.transform([clip]).view(B, n, 3, ingest.crop, ingest.crop))
 
     def _pieces(self, eng, src, tower):
         """pushes of at most max_push frames; the result is their concatenation"""
