@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, INGEST_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, INGEST_SIDE_LIBS, LIVE_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -54,12 +54,18 @@ MORE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%
 INGEST_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
                                   os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("ingest",)}
 
+# And the live gallery: the indexed cos_sim + OTAM kernel over a prototype store, running class sums and slot norms
+# (include/clipfsar_live.h).  A table of its own once more: tests/test_ingest_abi.py pins all_side_lib_names() and the staleness tuples over
+# it, so every_side_lib_names() names every side library and is what build() and _product_deps() walk.
+LIVE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
+                                os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("live",)}
+
 
 def side_lib(name) -> SideLib:
-    for table in (SIDE_LIBS, MORE_SIDE_LIBS):
+    for table in (SIDE_LIBS, MORE_SIDE_LIBS, INGEST_SIDE_LIBS):
         if name in table:
             return table[name]
-    return INGEST_SIDE_LIBS[name]
+    return LIVE_SIDE_LIBS[name]
 
 
 def side_lib_names() -> list:
@@ -69,6 +75,11 @@ def side_lib_names() -> list:
 def all_side_lib_names() -> list:
     """every side library: side_lib_names() (pinned by the older tests) and the tables added since"""
     return side_lib_names() + list(INGEST_SIDE_LIBS)
+
+
+def every_side_lib_names() -> list:
+    """every side library, the live gallery's included: all_side_lib_names() (pinned by tests/test_ingest_abi.py) and the tables added since"""
+    return all_side_lib_names() + list(LIVE_SIDE_LIBS)
 
 
 def _parse_usage(text: str) -> dict:
@@ -110,7 +121,7 @@ def _side_deps(name) -> list:
 def _product_deps() -> list:
     """every file of csrc/ that is not a side library's source or a header only side libraries include"""
     ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
-    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(side_lib, all_side_lib_names()))) - ours
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(side_lib, every_side_lib_names()))) - ours
     return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
 
@@ -168,7 +179,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
     The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        for name in all_side_lib_names():
+        for name in every_side_lib_names():
             build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):

@@ -14,21 +14,26 @@ __device__ __forceinline__ float4 load_row4(const float* __restrict__ X, size_t 
 }
 
 // The whole K loop of one workgroup's tile.  A / B: row-major [., E] operands (E % 4 == 0, 16-byte aligned rows); the tile's rows are
-// arow0 .. arow0 + a_rows - 1 of A and brow0 .. brow0 + b_rows - 1 of B (a_rows, b_rows <= TILE).  sA, sB: [TILE][SLD] staging buffers.
+// arow0 .. arow0 + a_rows - 1 of A (a_rows <= TILE) and, for tile row r of B, the row a B-ROW MAP names: brow(r), asked once per
+// staged row before the K loop, answers with a handle whose row() is the row of B and whose ok() says whether it exists (zeros are
+// staged when not).  What a handle computes late stays cheap in registers: the identity's (TileRows below) keeps only r.
+// sA, sB: [TILE][SLD] staging buffers.
 // acc[mi][ni]: this wave's 2 x 2 MFMA tiles (C/D map of the 16x16 MFMA: column = lane & 15, row = 4 (lane >> 4) + register), zeroed
 // here.  Ends with a barrier: on return every wave's fragment reads are done and the caller may overwrite the staging buffers.
-__device__ __forceinline__ void fp32_tile_gemm(const float* __restrict__ A, size_t arow0, int a_rows, const float* __restrict__ B,
-                                               size_t brow0, int b_rows, int E, float* sA, float* sB, f32x4 (&acc)[2][2]) {
+template <class BRowMap>
+__device__ __forceinline__ void fp32_tile_gemm_rows(const float* __restrict__ A, size_t arow0, int a_rows, const float* __restrict__ B,
+                                                    BRowMap brow, int E, float* sA, float* sB, f32x4 (&acc)[2][2]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // staging: 2 float4 of A and 2 of B per thread and chunk; rows / columns outside the operands are zero (they add +0 to the sums)
     const int sr0 = tid >> 3, sr1 = (tid + 256) >> 3, sc = (tid & 7) * 4;          // staged rows of the two float4s, their column
+    const auto br0 = brow(sr0), br1 = brow(sr1);                                   // the two staged B rows of this thread
     float4 ra0, ra1, rb0, rb1;
     auto load_chunk = [&](int k0) {
         const int col = k0 + sc;
         ra0 = load_row4(A, arow0 + sr0, col, E, sr0 < a_rows && col < E);
         ra1 = load_row4(A, arow0 + sr1, col, E, sr1 < a_rows && col < E);
-        rb0 = load_row4(B, brow0 + sr0, col, E, sr0 < b_rows && col < E);
-        rb1 = load_row4(B, brow0 + sr1, col, E, sr1 < b_rows && col < E);
+        rb0 = load_row4(B, br0.row(), col, E, br0.ok() && col < E);
+        rb1 = load_row4(B, br1.row(), col, E, br1.ok() && col < E);
     };
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
@@ -63,4 +68,28 @@ __device__ __forceinline__ void fp32_tile_gemm(const float* __restrict__ A, size
                     acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][s >> 2][s & 3], b[ni][s >> 2][s & 3], acc[mi][ni], 0, 0, 0);
     }
     __syncthreads();
+}
+
+// The identity map: the tile's B rows are brow0 .. brow0 + b_rows - 1 (b_rows <= TILE), as A's are.
+struct TileRows {
+    size_t row0;
+    int rows;
+    struct Row {
+        size_t row0;
+        int r, rows;
+        __device__ __forceinline__ size_t row() const { return row0 + r; }
+        __device__ __forceinline__ bool ok() const { return r < rows; }
+    };
+    __device__ __forceinline__ Row operator()(int r) const { return Row{row0, r, rows}; }
+};
+// A row looked up before the K loop (a gather through an index list): negative = no such row.
+struct LookedUpRow {
+    long long at;
+    __device__ __forceinline__ size_t row() const { return (size_t)at; }
+    __device__ __forceinline__ bool ok() const { return at >= 0; }
+};
+
+__device__ __forceinline__ void fp32_tile_gemm(const float* __restrict__ A, size_t arow0, int a_rows, const float* __restrict__ B,
+                                               size_t brow0, int b_rows, int E, float* sA, float* sB, f32x4 (&acc)[2][2]) {
+    fp32_tile_gemm_rows(A, arow0, a_rows, B, TileRows{brow0, b_rows}, E, sA, sB, acc);
 }

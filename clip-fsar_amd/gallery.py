@@ -18,7 +18,8 @@ Every arithmetic step runs on the HIP kernels: the engine's tower (HipViT / HipR
 sequences, class means, norms, the gallery cosine + OTAM and the top-k (libclipfsar_gallery.so, clip_fsar_amd.gallery_hip).
 
 The head's other two eval branches, TRAIN.EVAL_TEXT (zero-shot text matching) and TRAIN.COMBINE (text probabilities fused with these
-OTAM logits), are served by clip_fsar_amd.text_gallery.TextGallery, which shares the machinery below (_GalleryBase).
+OTAM logits), are served by clip_fsar_amd.text_gallery.TextGallery, which shares the machinery below (_GalleryBase).  A gallery whose classes also leave,
+receive further shots and are scored in subsets is clip_fsar_amd.live_gallery.LiveGallery.
 """
 from __future__ import annotations
 
@@ -167,8 +168,9 @@ class _GalleryBase:
             raise ValueError("%s: %d videos but %d class ids" % (self._name, videos.shape[0], len(ids_of_video)))
         return ids_of_video, list(dict.fromkeys(ids_of_video))
 
-    def _prototypes(self, eng, videos, ids_of_video, new_ids, trows):
-        """The visual prototypes [n, T, E] of the new classes and their frame-row norms [n * T] (few_shot.py:2944-2962)"""
+    def _support_sequences(self, eng, videos, ids_of_video, new_ids, trows):
+        """(X0 [Nv, T+1, E]: the support sequences grouped by class in the order of new_ids, video order inside a class; offs: the classes'
+        runs in it, len(new_ids) + 1 prefix sums).  The tower runs in the caller's video order."""
         Nv = videos.shape[0]
         n = len(new_ids)
         local = {c: i for i, c in enumerate(new_ids)}
@@ -185,21 +187,34 @@ class _GalleryBase:
         self._features(eng, videos, feats)
         feats = feats[torch.tensor(order, device=self.dev)].contiguous()
         cls_local = torch.tensor([local[ids_of_video[v]] for v in order], device=self.dev, dtype=torch.int32)
-        offsets = torch.tensor(offs, device=self.dev, dtype=torch.int32)
         X0 = torch.empty(Nv, T + 1, E, device=self.dev, dtype=torch.float32)
         ghip.support_sequences(feats, trows, cls_local, X0)
+        return X0, offs
+
+    def _context2_by_class(self, eng, seqs, seq_offs):
+        """context2 class by class (seqs [., T+1, E], class i = sequences seq_offs[i] .. seq_offs[i+1]-1): a class's prototype never depends
+        on how the classes were grouped into calls"""
+        T, E = self.T, self.E
+        Y = torch.empty_like(seqs)
+        for i in range(len(seq_offs) - 1):
+            s0, s1 = seq_offs[i], seq_offs[i + 1]
+            out = self._context2(eng, seqs[s0:s1], s1 - s0, T + 1, n_a_form=False)
+            Y[s0:s1].view(-1, E).copy_(out[:(s1 - s0) * (T + 1)])
+        return Y
+
+    def _prototypes(self, eng, videos, ids_of_video, new_ids, trows):
+        """The visual prototypes [n, T, E] of the new classes and their frame-row norms [n * T] (few_shot.py:2944-2962)"""
+        n = len(new_ids)
+        T, E = self.T, self.E
+        X0, offs = self._support_sequences(eng, videos, ids_of_video, new_ids, trows)
+        offsets = torch.tensor(offs, device=self.dev, dtype=torch.int32)
         if self.merge_before:                                 # class means BEFORE context2 (:2949-2954), the text row included
             seqs = torch.empty(n, T + 1, E, device=self.dev, dtype=torch.float32)
             ghip.segment_mean(X0, offsets, seqs)
             seq_offs = list(range(n + 1))
         else:
             seqs, seq_offs = X0, offs
-        # context2 class by class: a class's prototype never depends on how the classes were grouped into add_classes calls
-        Y = torch.empty_like(seqs)
-        for i in range(n):
-            s0, s1 = seq_offs[i], seq_offs[i + 1]
-            out = self._context2(eng, seqs[s0:s1], s1 - s0, T + 1, n_a_form=False)
-            Y[s0:s1].view(-1, E).copy_(out[:(s1 - s0) * (T + 1)])
+        Y = self._context2_by_class(eng, seqs, seq_offs)
         P = torch.empty(n, T, E, device=self.dev, dtype=torch.float32)
         # prototype = class mean of the first T rows (:2957-2962); with MERGE_BEFORE the one merged sequence's rows (a mean over one video)
         ghip.segment_mean(Y, offsets if not self.merge_before else torch.arange(n + 1, device=self.dev, dtype=torch.int32), P)
@@ -223,6 +238,10 @@ class _GalleryBase:
             raise ValueError("%s: feats must be [N, T=%d, E=%d], got %s" % (self._name, self.T, self.E, tuple(feats.shape)))
         return feats.to(dtype=torch.float32).contiguous()
 
+    def _n_columns(self):
+        """columns of the logits a classify call returns (LiveGallery: of the subset it was asked for)"""
+        return len(self._ids)
+
     def _scratch(self, nmax, C):
         """per-call buffers of _score for chunks of at most nmax clips"""
         return None
@@ -235,7 +254,7 @@ class _GalleryBase:
         if not self._ids:
             raise RuntimeError("%s: no classes registered" % self._name)
         src = self._check_videos(src, "queries") if tower else self._check_feats(src)
-        N, C = src.shape[0], len(self._ids)
+        N, C = src.shape[0], self._n_columns()
         out = torch.empty(N, C, device=self.dev, dtype=torch.float32)
         chunk = max(1, eng.max_frames // self.T)
         scratch = self._scratch(min(N, chunk), C)

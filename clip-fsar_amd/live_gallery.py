@@ -1,0 +1,397 @@
+"""Live gallery: a SupportGallery whose classes also leave, receive further shots, and are scored in subsets.
+
+SupportGallery keeps a dense P [C, T, E], so the column order is the memory order: every add_classes copies the whole gallery, a class
+cannot leave, and a caller who wants some of the classes pays for all.  Here the prototypes live in a STORE of slots and a column is a slot
+number (libclipfsar_live.so, clip_fsar_amd.live_hip): removal edits an int list, a subset is another list, further shots update one slot
+in place, and between growths (1.5 x when full) the store's address does not move.
+
+    g = LiveGallery(head, device, capacity=64)
+    g.add_classes(videos, class_of_video)        # SupportGallery's arguments, errors, return value -- and its prototypes, bit for bit
+    g.add_shots(videos, class_of_video)          # further examples of registered classes -> their shot counts
+    g.remove_classes([3, 7])                     # the other columns close up in their order; layout_version rises
+    logits = g.classify(queries, classes=[9, 2]) # [NQ, 2], columns in the order given; None: every class, in registration order
+    values, index = g.topk(queries, k=5, classes=None)
+    g.shots(9); g.state_dict()                   # SupportGallery's keys (dense, column order) + "sums" and "counts"
+
+A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
+support sequences before context2) and its shot count: further shots continue the sum in cfsg_segment_mean's operation order
+(cfsl_accumulate).  Serves the default eval branch, like SupportGallery, and is accepted wherever one is (WindowStream, StreamPool).
+"""
+from __future__ import annotations
+
+import collections
+import heapq
+
+import torch
+
+from . import gallery_hip as ghip
+from . import live_hip as lhip
+from .gallery import LAMBDA, _flag, _GalleryBase
+
+TABLE_ROWS = 1024                  # classes per descriptor table: larger updates go in pieces
+
+# ---------------------------------------------------------------------------------------------------------------- bookkeeping (pure)
+# Book: what the host knows about the store.  cap slots; free: a heap of the free ones (the lowest is taken first); order: the class ids
+# in column order; slot_of / shots: per registered id (shots 0: loaded without a sum, takes no further shots); version: rises with every
+# removal.  The plan_* functions below change nothing: they raise, or return the Book a call leaves behind together with what the device
+# work needs, and the caller installs the new Book once that work is queued.
+Book = collections.namedtuple("Book", "cap free order slot_of shots version")
+AddPlan = collections.namedtuple("AddPlan", "book slots")                 # slots: of the new classes, in their order
+RemovePlan = collections.namedtuple("RemovePlan", "book slots")           # slots: freed
+ShotPlan = collections.namedtuple("ShotPlan", "book classes rows")        # classes: first-appearance order; rows: (slot, off, n, prior)
+
+
+def new_book(cap):
+    return Book(int(cap), list(range(int(cap))), [], {}, {}, 0)
+
+
+def grown(cap, need):
+    """the capacity after growing 1.5 x until `need` more slots than cap holds fit"""
+    want = cap + need
+    while cap < want:
+        cap = max(cap + 1, cap * 3 // 2)
+    return cap
+
+
+def plan_add(book, ids, counts=None, name="LiveGallery"):
+    """ids: new classes, in order (counts: their shots, default 1 each) -> AddPlan.  The lowest free slots go to the classes in order;
+    a full store grows 1.5 x, its new slots free."""
+    ids = list(ids)
+    dup = [c for c in ids if c in book.slot_of]
+    if dup:
+        raise ValueError("%s: class %r is already registered" % (name, dup[0]))
+    if len(set(ids)) != len(ids):
+        raise ValueError("%s: a class appears twice among the new classes: %r" % (name, ids))
+    counts = [1] * len(ids) if counts is None else [int(c) for c in counts]
+    if len(counts) != len(ids) or any(c < 1 for c in counts):
+        raise ValueError("%s: every new class needs a shot count >= 1, got %r" % (name, counts))
+    cap, free = book.cap, list(book.free)
+    if len(ids) > len(free):
+        cap = grown(book.cap, len(ids) - len(free))
+        for s in range(book.cap, cap):
+            heapq.heappush(free, s)
+    slots = [heapq.heappop(free) for _ in ids]
+    slot_of, shots = dict(book.slot_of), dict(book.shots)
+    for c, s, k in zip(ids, slots, counts):
+        slot_of[c], shots[c] = s, k
+    return AddPlan(Book(cap, free, book.order + ids, slot_of, shots, book.version), slots)
+
+
+def _registered(book, ids, name, what):
+    ids = list(ids)
+    for c in ids:
+        if c not in book.slot_of:
+            raise ValueError("%s: class %r is not registered (%s)" % (name, c, what))
+    return ids
+
+
+def plan_remove(book, ids, name="LiveGallery"):
+    """ids: registered classes, each once -> RemovePlan.  Their slots become free, the other columns keep their order, version + 1."""
+    ids = _registered(book, ids, name, "remove_classes")
+    if len(set(ids)) != len(ids):
+        raise ValueError("%s: a class appears twice in remove_classes: %r" % (name, ids))
+    gone = set(ids)
+    free = list(book.free)
+    for c in ids:
+        heapq.heappush(free, book.slot_of[c])
+    slot_of = {c: s for c, s in book.slot_of.items() if c not in gone}
+    shots = {c: k for c, k in book.shots.items() if c not in gone}
+    return RemovePlan(Book(book.cap, free, [c for c in book.order if c not in gone], slot_of, shots, book.version + 1),
+                      [book.slot_of[c] for c in ids])
+
+
+def plan_shots(book, ids_of_video, name="LiveGallery"):
+    """ids_of_video: the class of every further video -> ShotPlan: per class in first-appearance order a row (slot, offset of its run among
+    the class-grouped videos, videos in the run, shots before)"""
+    ids_of_video = _registered(book, ids_of_video, name, "add_shots takes further videos of registered classes")
+    classes = list(dict.fromkeys(ids_of_video))
+    if not classes:
+        raise ValueError("%s: add_shots needs at least one video" % name)
+    for c in classes:
+        if book.shots[c] < 1:
+            raise ValueError("%s: class %r was loaded without its sum (a SupportGallery state): it takes no further shots -- remove it and "
+                             "add it again" % (name, c))
+    shots, rows, off = dict(book.shots), [], 0
+    for c in classes:
+        n = sum(1 for v in ids_of_video if v == c)
+        rows.append((book.slot_of[c], off, n, book.shots[c]))
+        shots[c] += n
+        off += n
+    return ShotPlan(book._replace(shots=shots), classes, rows)
+
+
+def plan_columns(book, classes=None, name="LiveGallery"):
+    """the slots of the columns of a classify call: every class in column order, or `classes` in the order given (registered, no repeats)"""
+    if classes is None:
+        return [book.slot_of[c] for c in book.order]
+    classes = _registered(book, classes, name, "classes=")
+    if not classes:
+        raise ValueError("%s: classes= needs at least one class" % name)
+    if len(set(classes)) != len(classes):
+        raise ValueError("%s: a class appears twice in classes=: %r" % (name, classes))
+    return [book.slot_of[c] for c in classes]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the gallery
+class LiveGallery(_GalleryBase):
+    def __init__(self, head, device="cuda", capacity=64):
+        head = getattr(head, "head", head)                 # BaseVideoModel -> its CNN_OTAM_CLIPFSAR head
+        cfg = head.args
+        for flag in ("EVAL_TEXT", "COMBINE"):
+            if _flag(cfg.TRAIN, flag):
+                raise NotImplementedError("LiveGallery: TRAIN.%s is not supported -- the gallery serves the default eval branch (cosine + "
+                                          "OTAM of context2 features) only; use clip_fsar_amd.text_gallery.TextGallery for this branch" % flag)
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+            raise ValueError("LiveGallery: capacity must be an integer >= 1, got %r" % (capacity,))
+        self._setup(head, device)
+        if self.T > lhip.MAX_T:
+            raise ValueError("LiveGallery: T = %d frames, the live library scores at most %d" % (self.T, lhip.MAX_T))
+        self._capacity = capacity
+        self._store = None                                 # allocated by the first call that needs the device
+        self._retired = []                                 # (outgrown store, the event behind the work queued on it)
+        self._tables = None
+        self._book = self._active = None
+        self.clear()
+
+    # ------------------------------------------------------------------ state
+    def clear(self):
+        """Drop every class (and bind to the head's current engine).  The store keeps its memory."""
+        self._bind()
+        version = 0 if self._book is None else self._book.version + bool(self._book.order)
+        cap = self._store["P"].shape[0] if self._store is not None else self._capacity
+        self._install(new_book(cap)._replace(version=version))
+
+    def _install(self, book):
+        self._book = book
+        self._ids = book.order                             # _GalleryBase: len(), class_ids, "no classes registered"
+        self._cols = None                                  # device column list of all classes, made on demand
+        self._subset = (None, None)                        # the last classes= list and its device columns
+
+    @property
+    def layout_version(self):
+        """rises whenever a column may have changed its meaning: on every remove_classes (and a clear() of a non-empty gallery)"""
+        return self._book.version
+
+    @property
+    def capacity(self):
+        return self._book.cap
+
+    def shots(self, cid):
+        """the shot count of a class (0: loaded from a SupportGallery state, whose sums are not known)"""
+        if cid not in self._book.shots:
+            raise ValueError("LiveGallery: class %r is not registered (shots)" % (cid,))
+        return self._book.shots[cid]
+
+    def slot_of(self, cid):
+        return self._book.slot_of[cid]
+
+    # ------------------------------------------------------------------ the store
+    def _rows(self):
+        return self.T + 1                                  # rows of a support sequence, and of a slot of `sums`
+
+    def _alloc(self, cap):
+        T, E, f = self.T, self.E, dict(device=self.dev, dtype=torch.float32)
+        return {"P": torch.empty(cap, T, E, **f), "pn": torch.empty(cap * T, **f), "text": torch.empty(cap, E, **f),
+                "sums": torch.empty(cap, self._rows(), E, **f)}
+
+    def _ensure_store(self, cap):
+        """the store with at least cap slots.  Growth copies the old slots once; the outgrown buffers are kept until the work queued on
+        them (a classify in flight) is done."""
+        self._retired = [(b, e) for b, e in self._retired if not e.query()]
+        old = self._store
+        if old is not None and old["P"].shape[0] >= cap:
+            return old
+        new = self._alloc(cap)
+        if old is not None:
+            c0 = old["P"].shape[0]
+            for k in ("P", "text", "sums"):
+                new[k][:c0].copy_(old[k])
+            new["pn"][:c0 * self.T].copy_(old["pn"])
+            with torch.cuda.device(self.dev):
+                ev = torch.cuda.Event()
+                ev.record()
+            self._retired.append((old, ev))
+        self._store = new
+        return new
+
+    def _upload(self, rows):
+        if self._tables is None:
+            self._tables = lhip.table_uploader(self.dev, TABLE_ROWS)
+        return self._tables.upload([list(r) for r in rows])
+
+    def _update(self, eng, videos, ids_of_video, classes, trows, rows):
+        """videos of `classes` (first-appearance order; rows: their (slot, off, n, prior)) into the store: sums, prototypes, norms.
+        SupportGallery's launch sequence -- tower in the caller's order, context2 class by class -- with cfsl_accumulate in the place of
+        cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone."""
+        st, T, E, n = self._store, self.T, self.E, len(classes)
+        X0, offs = self._support_sequences(eng, videos, ids_of_video, classes, trows)
+        Y = None if self.merge_before else self._context2_by_class(eng, X0, offs)       # (:2955-2956)
+        for c0 in range(0, n, TABLE_ROWS):
+            c1 = min(n, c0 + TABLE_ROWS)
+            v0, v1 = offs[c0], offs[c1]
+            table = self._upload([(s, o - v0, k, p) for s, o, k, p in rows[c0:c1]])
+            if self.merge_before:                             # class means BEFORE context2 (:2949-2954), the text row included
+                seqs = torch.empty(c1 - c0, T + 1, E, device=self.dev, dtype=torch.float32)
+                lhip.accumulate(X0[v0:v1], st["sums"], seqs, table, by_slot=False)
+                Y1 = self._context2_by_class(eng, seqs, list(range(c1 - c0 + 1)))
+                P = torch.empty(c1 - c0, T, E, device=self.dev, dtype=torch.float32)
+                ghip.segment_mean(Y1, torch.arange(c1 - c0 + 1, device=self.dev, dtype=torch.int32), P)     # a mean over one sequence
+                st["P"].index_copy_(0, torch.tensor([r[0] for r in rows[c0:c1]], device=self.dev), P)
+            else:                                             # prototype = class mean of context2's first T rows (:2957-2962)
+                lhip.accumulate(Y[v0:v1], st["sums"], st["P"], table, by_slot=True)
+            lhip.slot_norms(st["P"], st["pn"], table)
+
+    # ------------------------------------------------------------------ registration, shots, removal
+    def add_classes(self, videos, class_of_video, text=None):
+        """SupportGallery.add_classes: the same arguments, errors, return value (the new classes' column indices) and prototypes; nothing but
+        the new classes is written."""
+        eng = self._fresh_engine()
+        videos = self._check_videos(videos, "videos")
+        ids_of_video, new_ids = self._video_classes(videos, class_of_video, text)
+        trows = self._text_rows(eng, new_ids, text)
+        counts = [sum(1 for v in ids_of_video if v == c) for c in new_ids]
+        plan = plan_add(self._book, new_ids, counts, self._name)
+        st = self._ensure_store(plan.book.cap)
+        offs = [0]
+        for k in counts:
+            offs.append(offs[-1] + k)
+        self._update(eng, videos, ids_of_video, new_ids, trows, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)])
+        st["text"].index_copy_(0, torch.tensor(plan.slots, device=self.dev), trows)
+        C0 = len(self._book.order)
+        self._install(plan.book)
+        return list(range(C0, C0 + len(new_ids)))
+
+    def add_shots(self, videos, class_of_video):
+        """Further videos [Nv, T, 3, H, W] of registered classes (class_of_video [Nv]) join their classes after the existing shots: the
+        classes' sums go on, their prototypes and norms are recomputed in place.  Returns the classes' shot counts, in first-appearance
+        order."""
+        eng = self._fresh_engine()
+        videos = self._check_videos(videos, "videos")
+        ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (
+            class_of_video.reshape(-1).cpu() if isinstance(class_of_video, torch.Tensor) else class_of_video)]
+        ids = [int(c) if isinstance(c, float) and c == int(c) else c for c in ids]
+        if len(ids) != videos.shape[0]:
+            raise ValueError("%s: %d videos but %d class ids" % (self._name, videos.shape[0], len(ids)))
+        plan = plan_shots(self._book, ids, self._name)
+        st = self._store
+        trows = st["text"].index_select(0, torch.tensor([r[0] for r in plan.rows], device=self.dev))
+        self._update(eng, videos, ids, plan.classes, trows, plan.rows)
+        self._book = plan.book                              # the columns did not change: _ids and the device lists stay
+        return [plan.book.shots[c] for c in plan.classes]
+
+    def remove_classes(self, ids):
+        """Drop registered classes: their slots become free (the lowest free slot is the next one taken), the remaining columns close up
+        in their order, no prototype moves.  layout_version rises.  Unknown ids raise before anything changes."""
+        ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (ids.reshape(-1).cpu() if isinstance(ids, torch.Tensor) else ids)]
+        self._install(plan_remove(self._book, ids, self._name).book)
+
+    # ------------------------------------------------------------------ classification
+    def _columns(self, classes):
+        """device int32 column list of a call (raises on unknown or repeated ids)"""
+        if classes is None:
+            if self._cols is None:
+                self._cols = torch.tensor(plan_columns(self._book), device=self.dev, dtype=torch.int32)
+            return self._cols
+        classes = list(classes)
+        slots = plan_columns(self._book, classes, self._name)
+        key = tuple(slots)
+        if self._subset[0] != key:
+            self._subset = (key, torch.tensor(slots, device=self.dev, dtype=torch.int32))
+        return self._subset[1]
+
+    def _n_columns(self):
+        return self._active.shape[0]
+
+    def _classify_cols(self, src, tower, classes):
+        classes = None if classes is None else list(classes)
+        self._fresh_engine()
+        if not self._ids:
+            raise RuntimeError("%s: no classes registered" % self._name)
+        if classes is not None:
+            plan_columns(self._book, classes, self._name)     # every error before the device is touched
+        src = self._check_videos(src, "queries") if tower else self._check_feats(src)
+        self._active = self._columns(classes)
+        try:
+            return self._classify(src, tower)
+        finally:
+            self._active = None
+
+    def classify(self, queries, classes=None):
+        """queries [NQ, T, 3, H, W] fp32 (device) -> logits [NQ, C] fp32 against every registered class in registration order, or against
+        `classes` (registered ids, any order, no repeats) -> [NQ, len(classes)], columns in the order given"""
+        return self._classify_cols(queries, True, classes)
+
+    def classify_features(self, feats, classes=None):
+        """feats [N, T, E] fp32 (device), the tower features of N clips -> the logits classify gives for those clips"""
+        return self._classify_cols(feats, False, classes)
+
+    def topk(self, queries, k=5, classes=None):
+        """(values [NQ, k] fp32 descending, index [NQ, k] int32 into class_ids -- into `classes` when given); ties go to the lower index"""
+        classes = None if classes is None else list(classes)
+        C = len(self._ids) if classes is None else len(plan_columns(self._book, classes, self._name))
+        if not 1 <= k <= min(ghip.TOPK_MAX, max(1, C)):
+            raise ValueError("%s.topk: k must be in [1, min(16, number of classes)], got %d" % (self._name, k))
+        logits = self.classify(queries, classes)
+        values = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.float32)
+        index = torch.empty(logits.shape[0], k, device=self.dev, dtype=torch.int32)
+        ghip.topk(logits, k, values, index)
+        return values, index
+
+    def _score(self, eng, feats, n, ws, out, scratch):
+        T, st = self.T, self._store
+        Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
+        ghip.row_norms(Xq, ws["qn"])
+        lhip.otam_indexed(Xq, ws["qn"], st["P"], st["pn"], self._active, out, LAMBDA, self.single_direct)
+
+    # ------------------------------------------------------------------ state dict
+    def state_dict(self):
+        """SupportGallery's keys, dense and in column order (SupportGallery.load_state_dict accepts it), plus "sums" [C, T+1, E] and
+        "counts" [C] (0: no sum known)"""
+        book = self._book
+        C = len(book.order)
+        if C:
+            idx = torch.tensor(plan_columns(book), device=self.dev)
+            st = self._store
+            P, text, sums = (st[k].index_select(0, idx).cpu() for k in ("P", "text", "sums"))
+            pn = st["pn"].view(-1, self.T).index_select(0, idx).reshape(-1).cpu()
+        else:
+            P, pn = torch.empty(0, self.T, self.E), torch.empty(0)
+            text, sums = torch.empty(0, self.E), torch.empty(0, self._rows(), self.E)
+        return {"fingerprint": self.fingerprint(), "class_ids": list(book.order), "prototypes": P, "norms": pn, "text": text, "sums": sums,
+                "counts": [book.shots[c] for c in book.order]}
+
+    def load_state_dict(self, sd):
+        """a LiveGallery's or a SupportGallery's state.  Classes without sums (a SupportGallery's) score normally and take no further shots."""
+        if sd["fingerprint"] != self.fingerprint():
+            raise ValueError("LiveGallery.load_state_dict: fingerprint %s does not match this gallery's %s" % (sd["fingerprint"],
+                                                                                                                 self.fingerprint()))
+        ids = list(sd["class_ids"])
+        C, T, E = len(ids), self.T, self.E
+        P, pn, text = sd["prototypes"], sd["norms"], sd["text"]
+        if tuple(P.shape) != (C, T, E) or tuple(pn.shape) != (C * T,) or tuple(text.shape) != (C, E):
+            raise ValueError("LiveGallery.load_state_dict: inconsistent shapes %s %s %s for %d classes" % (
+                tuple(P.shape), tuple(pn.shape), tuple(text.shape), C))
+        sums, counts = sd.get("sums"), sd.get("counts")
+        if (sums is None) != (counts is None):
+            raise ValueError("LiveGallery.load_state_dict: \"sums\" and \"counts\" come together")
+        if sums is not None:
+            counts = [int(c) for c in counts]
+            if tuple(sums.shape) != (C, self._rows(), E) or len(counts) != C or any(c < 0 for c in counts):
+                raise ValueError("LiveGallery.load_state_dict: inconsistent sums %s / %d counts for %d classes" % (
+                    tuple(sums.shape), len(counts), C))
+        if len(set(ids)) != C:
+            raise ValueError("LiveGallery.load_state_dict: a class id appears twice")
+        self._bind()
+        old_version = self._book.version
+        book = new_book(max(self._capacity, C, self._store["P"].shape[0] if self._store is not None else 0))
+        if C:
+            plan = plan_add(book, ids, None, self._name)
+            book = plan.book._replace(shots=dict(zip(ids, counts if sums is not None else [0] * C)))
+            st = self._ensure_store(book.cap)
+            f32 = lambda t: t.to(device=self.dev, dtype=torch.float32)
+            st["P"][:C].copy_(f32(P))
+            st["pn"][:C * T].copy_(f32(pn))
+            st["text"][:C].copy_(f32(text))
+            if sums is not None:
+                st["sums"][:C].copy_(f32(sums))
+        self._install(book._replace(version=old_version + 1))

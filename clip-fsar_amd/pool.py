@@ -76,7 +76,7 @@ def plan_push(sessions, counts, T, stride, rate, max_push, smoothing=False):
 
 
 class _Session:
-    __slots__ = ("slot", "t", "tower_frames", "state_gen")
+    __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout")
 
     def __init__(self, slot):
         self.slot = slot
@@ -86,6 +86,7 @@ class _Session:
         self.t = 0                               # frames pushed since open() / reset()
         self.tower_frames = 0
         self.state_gen = None                    # generation of the pool's smoothing buffer this session's state row was written in
+        self.state_layout = None                 # the gallery's layout_version then (None: a gallery whose columns never change meaning)
 
 
 class StreamPool:
@@ -199,6 +200,10 @@ class StreamPool:
                 if s.state_gen is not None and (fresh or s.state_gen != self._state_gen):
                     raise RuntimeError("StreamPool: the gallery has %d classes, the smoothing state of session %d was made with another "
                                        "count -- reset() the session after adding classes when smoothing is on" % (C, h))
+                if s.state_gen is not None and s.state_layout != getattr(self.gallery, "layout_version", None):
+                    raise RuntimeError("StreamPool: classes were removed from the gallery since the smoothing state of session %d was "
+                                       "made, its columns mean other classes now -- reset() the session after removing classes when "
+                                       "smoothing is on" % h)
 
     def push_packed(self, frames, sessions, counts):
         """frames [N, 3, H, W] fp32 (device): counts[i] next frames of sessions[i], one session after the other -> PackedOutput of the
@@ -324,6 +329,7 @@ class StreamPool:
             s.t += n
             if self.alpha and nW:
                 s.state_gen = self._state_gen
+                s.state_layout = getattr(g, "layout_version", None)
             offsets.append(offsets[-1] + nW)
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += NW

@@ -80,6 +80,7 @@ class WindowStream:
         self._t = 0
         self._tower_frames = 0
         self._state = None                       # smoothing state [B, C]
+        self._state_layout = None                # the gallery's layout_version when it was made (None: a gallery without one)
 
     @property
     def stats(self):
@@ -170,6 +171,9 @@ class WindowStream:
         if self.alpha and self._state is not None and self._state.shape[1] != C:
             raise RuntimeError("WindowStream: the gallery has %d classes, the smoothing state %d -- reset() the stream after adding "
                                "classes when smoothing is on" % (C, self._state.shape[1]))
+        if self.alpha and self._state is not None and self._state_layout != getattr(g, "layout_version", None):
+            raise RuntimeError("WindowStream: classes were removed from the gallery since the smoothing state was made, its columns mean "
+                               "other classes now -- reset() the stream after removing classes when smoothing is on")
         first, nW = window_plan(self._t, n, T, self.stride, self.rate)
         shp.ring_put(feats, self._ring, self._t)
         self._t += n
@@ -190,6 +194,7 @@ class WindowStream:
             return logits, None
         if self._state is None:
             self._state = torch.empty(B, C, device=self.dev, dtype=torch.float32)
+            self._state_layout = getattr(g, "layout_version", None)
         smoothed = torch.empty_like(logits)
         shp.smooth_logits(logits, self._state, smoothed, self.alpha, first)
         return logits, smoothed
