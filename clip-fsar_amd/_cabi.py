@@ -1,7 +1,9 @@
-"""What the six ctypes bindings (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip) share: loading a C-ABI library against its signature table, and the
-builders of their ``_check`` / ``_shape`` helpers.  Each binding keeps its own SIGNATURES, ABI_VERSION, LIB_PATH and ``lib()``."""
+"""What the seven ctypes bindings (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip) share: loading a C-ABI
+library against its signature table, the builders of their ``_check`` / ``_shape`` helpers, and the descriptor table that three of them
+pass.  Each binding keeps its own SIGNATURES, ABI_VERSION, LIB_PATH and ``lib()``."""
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -41,3 +43,16 @@ def shape_checker(module):
         if tuple(t.shape) != tuple(shape):
             raise RuntimeError("clip_fsar_amd.%s: %s has shape %s, expected %s" % (module, name, tuple(t.shape), tuple(shape)))
     return _shape
+
+
+Table = collections.namedtuple("Table", "host dev S")          # host: pinned [S, cols] int32 rows; dev: their device copy
+
+
+def table_args(t, cols, module):
+    """(host pointer, device pointer, S) of a Table of ``cols`` values per row, as the table_host / table_dev / S arguments of a call"""
+    import torch
+    from .hip import _dev
+    if not isinstance(t, Table) or t.host.is_cuda or t.host.dtype != torch.int32 or tuple(t.host.shape) != (t.S, cols) \
+            or not t.host.is_contiguous() or tuple(t.dev.shape) != (t.S, cols):
+        raise RuntimeError("clip_fsar_amd.%s: table must be a Table of [S, %d] int32 host rows and their device copy" % (module, cols))
+    return ctypes.c_void_p(t.host.data_ptr()), _dev(t.dev, torch.int32, "table"), t.S

@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, INGEST_SIDE_LIBS, LIVE_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -35,51 +35,19 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
-# The side libraries: the support gallery (include/clipfsar_gallery.h), its text half, the EVAL_TEXT / COMBINE kernels
-# (include/clipfsar_gallery_text.h), and the window streams' ring, gather and smoothing kernels (include/clipfsar_stream.h).  Each is ONE
-# source compiled with the product FLAGS and the fence into a library of its own beside libclipfsar_hip.so (the pinned export sets stay
-# apart), with its own staleness check and its own resource report (build/resource_usage.json stays the product library's).
-SideLib = collections.namedtuple("SideLib", "source lib usage")        # the C header (include/clipfsar_<name>.h) is a dependency through #include
+# The side libraries, in the order they are built: the support gallery, its text half (EVAL_TEXT / COMBINE), the window streams' ring,
+# gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, and the live gallery; C ABI of each in
+# include/clipfsar_<name>.h.  Each is ONE source, csrc/<name>.hip, compiled with the product FLAGS and the fence into a library of its own
+# beside libclipfsar_hip.so (the pinned export sets stay apart), stale when a file its source reaches through #include is newer, with its
+# own resource report (build/resource_usage.json stays the product library's).  A further library is one more name here.
+SideLib = collections.namedtuple("SideLib", "source lib usage")
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                           os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("gallery", "gallery_text", "stream")}
-# Side libraries added after the three above, same recipe: the stream pool's ring, gather and smoothing kernels over a per-session descriptor
-# table (include/clipfsar_pool.h).  A table of its own: tests/test_stream_abi.py pins list(SIDE_LIBS) and the staleness tuples over it.
-MORE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                                os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("pool",)}
-
-
-# And after those: frame ingest, the test-time frame transform over uint8 clips of mixed geometry in one launch (include/clipfsar_ingest.h).
-# Again a table of its own: tests/test_pool_abi.py pins side_lib_names() and the staleness tuples over it, so the libraries of this table
-# are named by all_side_lib_names() alone, which is what build() and _product_deps() walk.
-INGEST_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                                  os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("ingest",)}
-
-# And the live gallery: the indexed cos_sim + OTAM kernel over a prototype store, running class sums and slot norms
-# (include/clipfsar_live.h).  A table of its own once more: tests/test_ingest_abi.py pins all_side_lib_names() and the staleness tuples over
-# it, so every_side_lib_names() names every side library and is what build() and _product_deps() walk.
-LIVE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                                os.path.join(HERE, "build", name, "resource_usage.json")) for name in ("live",)}
-
-
-def side_lib(name) -> SideLib:
-    for table in (SIDE_LIBS, MORE_SIDE_LIBS, INGEST_SIDE_LIBS):
-        if name in table:
-            return table[name]
-    return LIVE_SIDE_LIBS[name]
+                           os.path.join(HERE, "build", name, "resource_usage.json"))
+             for name in ("gallery", "gallery_text", "stream", "pool", "ingest", "live")}
 
 
 def side_lib_names() -> list:
-    return list(SIDE_LIBS) + list(MORE_SIDE_LIBS)
-
-
-def all_side_lib_names() -> list:
-    """every side library: side_lib_names() (pinned by the older tests) and the tables added since"""
-    return side_lib_names() + list(INGEST_SIDE_LIBS)
-
-
-def every_side_lib_names() -> list:
-    """every side library, the live gallery's included: all_side_lib_names() (pinned by tests/test_ingest_abi.py) and the tables added since"""
-    return all_side_lib_names() + list(LIVE_SIDE_LIBS)
+    return list(SIDE_LIBS)
 
 
 def _parse_usage(text: str) -> dict:
@@ -115,13 +83,13 @@ def _includes(path, seen=None) -> set:
 
 
 def _side_deps(name) -> list:
-    return sorted(_includes(os.path.join(CSRC, side_lib(name).source))) + [os.path.abspath(__file__)]
+    return sorted(_includes(os.path.join(CSRC, SIDE_LIBS[name].source))) + [os.path.abspath(__file__)]
 
 
 def _product_deps() -> list:
     """every file of csrc/ that is not a side library's source or a header only side libraries include"""
     ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
-    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(side_lib, every_side_lib_names()))) - ours
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in SIDE_LIBS.values())) - ours
     return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
 
@@ -165,8 +133,8 @@ def _link(lib, objs, usage, usage_path, verbose) -> str:
 
 
 def build_side(name, force: bool = False, verbose: bool = True) -> str:
-    """side_lib(name): its one source -> its own library with the product FLAGS and the packed-fp32 fence, resource report -> .usage"""
-    sl = side_lib(name)
+    """SIDE_LIBS[name]: its one source -> its own library with the product FLAGS and the packed-fp32 fence, resource report -> .usage"""
+    sl = SIDE_LIBS[name]
     if not force and not _stale(sl.lib, _side_deps(name)):
         return sl.lib
     bdir = os.path.dirname(sl.usage)
@@ -179,7 +147,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
     The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        for name in every_side_lib_names():
+        for name in SIDE_LIBS:
             build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):

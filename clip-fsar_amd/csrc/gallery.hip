@@ -2,9 +2,7 @@
 // per-class means over contiguous runs of videos, row norms, top-k, and the hot kernel -- cos_sim + OTAM of every (query, class)
 // pair of a gallery (few_shot.py:1115-1124, 2657-2687, 2970-2990) as one exact-fp32 MFMA GEMM with the soft-min DPs in its epilogue.
 // A library of its own: libclipfsar_hip.so keeps exactly the entry points of include/clipfsar_hip.h.
-#include "fp32_tile_gemm.h"
-#include "otam_dp.h"
-#include "side_lib.h"
+#include "otam_tile.h"
 #include "../../include/clipfsar_gallery.h"
 
 namespace {
@@ -54,84 +52,23 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict_
     if (lane == 0) n[r] = sqrtf(ss);
 }
 
-// ---- cos_sim + OTAM of a gallery.  A workgroup (4 waves) owns QB queries x QB classes: a TILE x TILE block of frame rows
-// (T = 8: 8 x 8 videos, 64 pairs; T = 16: 4 x 4).
-//   GEMM: [QB*T, E] x [QB*T, E]^T, fp32_tile_gemm (fp32_tile_gemm.h).
-//   Epilogue: d = 1 - dot / (qn pn + 0.01) into an LDS image of the tile (aliasing the staging buffers), then one lane per
-//   (pair, direction) runs the DP -- rows in registers for T = 8 / 16, in an LDS slot per thread for run-time T.
-constexpr int DLD = TILE + 1 /* distance image */;
-constexpr int MAX_PAIRS = 256;
-
-__host__ __device__ inline int tile_videos(int T) { return TILE / T < 16 ? TILE / T : 16; }
-__host__ __device__ inline int dp_slots(int T) {
-    const int lanes = 2 * tile_videos(T) * tile_videos(T);
-    return lanes < 256 ? lanes : 256;
-}
-// LDS floats: staging (A | B; the distance image reuses it) + norms + DP results (+ run-time-T DP rows)
-__host__ __device__ inline int gallery_lds_floats(int T, bool fixed_t) {
-    return 2 * TILE * SLD + 2 * TILE + 2 * MAX_PAIRS + (fixed_t ? 0 : dp_slots(T) * 2 * (T + 2));
-}
+// ---- cos_sim + OTAM of a gallery: otam_tile (otam_tile.h) over dense classes -- tile row r of B is row c0 * T + r of P (the identity map
+// of fp32_tile_gemm.h), its norm the same row of pn
+struct DenseClasses {
+    const float* __restrict__ pn;
+    float* __restrict__ dists_out;
+    static constexpr bool POISONS = false;
+    __device__ __forceinline__ TileRows::Row row(int r, int c0, int b_rows, int T) const { return TileRows{(size_t)c0 * T, b_rows}(r); }
+    __device__ __forceinline__ float norm(int r, int c0, int b_rows, int T) const { return r < b_rows ? pn[(size_t)c0 * T + r] : 1.f; }
+    __device__ __forceinline__ float* dists() const { return dists_out; }
+};
 
 template <int TT>
 __global__ __launch_bounds__(256) void otam_gallery_kernel(const float* __restrict__ Xq, const float* __restrict__ qn,
                                                            const float* __restrict__ P, const float* __restrict__ pn,
                                                            float* __restrict__ logits, float* __restrict__ dists_out, int NQ, int C,
                                                            int Trt, int E, float lbda, int single_direct) {
-    static_assert(TILE * DLD <= 2 * TILE * SLD, "the distance image must fit into the staging buffers");
-    const int T = TT > 0 ? TT : Trt;
-    const int QB = tile_videos(T);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* sA = smem;                                  // [TILE][SLD]
-    float* sB = smem + TILE * SLD;                     // [TILE][SLD]
-    float* dist = smem;                                // [TILE][DLD], after the K loop
-    float* sqn = smem + 2 * TILE * SLD;                // [TILE]
-    float* spn = sqn + TILE;                           // [TILE]
-    float* res = spn + TILE;                           // [2 * MAX_PAIRS]
-    float* dprows = res + 2 * MAX_PAIRS;               // TT == 0: [dp_slots][2][T + 2]
-    const int c0 = blockIdx.x * QB, q0 = blockIdx.y * QB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t arow0 = (size_t)q0 * T, brow0 = (size_t)c0 * T;
-    const int a_rows = min(QB, NQ - q0) * T, b_rows = min(QB, C - c0) * T;        // valid frame rows of each operand
-    if (tid < TILE) sqn[tid] = tid < a_rows ? qn[arow0 + tid] : 1.f;
-    else if (tid < 2 * TILE) spn[tid - TILE] = tid - TILE < b_rows ? pn[brow0 + tid - TILE] : 1.f;
-
-    f32x4 acc[2][2];
-    fp32_tile_gemm(Xq, arow0, a_rows, P, brow0, b_rows, E, sA, sB, acc);      // ends with a barrier: the distance image overwrites the staging buffers
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, fr = lane & 15, fh = lane >> 4;
-    // C/D map of the 16x16 MFMA: column = lane & 15, row = 4 (lane >> 4) + register
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int row = wm + 16 * mi + 4 * fh + g, col = wn + 16 * ni + fr;
-                dist[row * DLD + col] = 1.0f - acc[mi][ni][g] / (sqn[row] * spn[col] + 0.01f);
-            }
-    __syncthreads();
-    const int npairs = QB * QB, TT2 = T * T;
-    if (dists_out) {
-        for (int i = tid; i < npairs * TT2; i += 256) {
-            const int pair = i / TT2, lm = i - pair * TT2, qi = pair / QB, cj = pair - qi * QB, l = lm / T, m = lm - l * T;
-            if (q0 + qi < NQ && c0 + cj < C)
-                dists_out[((size_t)(q0 + qi) * C + (c0 + cj)) * TT2 + lm] = dist[(qi * T + l) * DLD + cj * T + m];
-        }
-    }
-    for (int p = tid; p < 2 * npairs; p += 256) {
-        const int pair = p >> 1, dir = p & 1, qi = pair / QB, cj = pair - qi * QB;
-        float v = 0.f;
-        if (q0 + qi < NQ && c0 + cj < C && !(dir && single_direct)) {
-            const float* d = dist + qi * T * DLD + cj * T;
-            // dir 0: rows = query frames; dir 1: the transposed distances (:2982)
-            v = otam_dp<TT>(d, dir ? 1 : DLD, dir ? DLD : 1, T, lbda, dprows + tid * 2 * (T + 2), T + 2);
-        }
-        res[p] = v;
-    }
-    __syncthreads();
-    for (int pair = tid; pair < npairs; pair += 256) {
-        const int qi = pair / QB, cj = pair - qi * QB;
-        if (q0 + qi < NQ && c0 + cj < C) logits[(size_t)(q0 + qi) * C + (c0 + cj)] = -(res[2 * pair] + res[2 * pair + 1]);
-    }
+    otam_tile<TT>(Xq, qn, P, DenseClasses{pn, dists_out}, logits, NQ, C, Trt, E, lbda, single_direct);
 }
 
 // ---- top-k per query: one wave per query.  Each lane keeps the best KMAX of its strided classes (a compare-exchange chain with
@@ -221,23 +158,12 @@ extern "C" int cfsg_row_norms(const float* X, float* n, int R, int E, cfsg_strea
 extern "C" int cfsg_otam_gallery(const float* Xq, const float* qn, const float* P, const float* pn, float* logits, float* dists_out, int NQ,
                                  int C, int T, int E, float lambda, int single_direct, cfsg_stream_t stream) {
     SIDE_REQUIRE(Xq && qn && P && pn && logits, "cfsg_otam_gallery: null pointer");
-    SIDE_REQUIRE(NQ > 0 && C > 0 && T > 0 && T <= MAX_T && E >= 4 && E <= 8192 && E % 4 == 0,
-                 "cfsg_otam_gallery: bad shape (NQ=%d C=%d T=%d E=%d; T <= 32, E %% 4 == 0, 4 <= E <= 8192)", NQ, C, T, E);
-    SIDE_REQUIRE(lambda > 0.f, "cfsg_otam_gallery: lambda must be > 0");
-    const int qb = tile_videos(T);
-    const long long gx = ((long long)C + qb - 1) / qb, gy = ((long long)NQ + qb - 1) / qb;
-    SIDE_REQUIRE(gy <= 65535, "cfsg_otam_gallery: NQ=%d too large for one launch (at most %d at T=%d)", NQ, 65535 * qb, T);
-    const bool fixed_t = T == 8 || T == 16;                   // DP rows in registers; otherwise in an LDS slot per thread
-    const int lds = gallery_lds_floats(T, fixed_t) * (int)sizeof(float);
-    SIDE_REQUIRE(lds <= 48 * 1024, "cfsg_otam_gallery: LDS %d bytes", lds);
-    auto launch = [&](auto kern) -> int {
-        hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, static_cast<hipStream_t>(stream), Xq, qn, P, pn, logits,
-                           dists_out, NQ, C, T, E, lambda, single_direct);
-        return check_launch("cfsg_otam_gallery");
-    };
-    if (T == 8) return launch(&otam_gallery_kernel<8>);
-    if (T == 16) return launch(&otam_gallery_kernel<16>);
-    return launch(&otam_gallery_kernel<0>);
+    SIDE_REQUIRE(otam_shape_ok(NQ, C, T, E), "cfsg_otam_gallery: bad shape (NQ=%d C=%d T=%d E=%d; T <= 32, E %% 4 == 0, 4 <= E <= 8192)", NQ, C,
+                 T, E);
+    return otam_tile_launch("cfsg_otam_gallery", NQ, C, T, lambda, [&](auto tt, dim3 grid, int lds) {
+        hipLaunchKernelGGL(otam_gallery_kernel<decltype(tt)::value>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), Xq, qn, P, pn,
+                           logits, dists_out, NQ, C, T, E, lambda, single_direct);
+    });
 }
 
 extern "C" int cfsg_topk(const float* logits, float* values, int32_t* index, int NQ, int C, int k, cfsg_stream_t stream) {

@@ -1,5 +1,6 @@
-// OTAM soft-min DP (few_shot.py:2657-2687), un-stabilised like the reference: the one recurrence of cos_otam_kernel (tail.hip) and
-// otam_gallery_kernel (gallery.hip), so equal distance blocks give bit-equal results in both.
+// OTAM soft-min DP (few_shot.py:2657-2687), un-stabilised like the reference: the one recurrence of cos_otam_kernel (tail.hip) and of
+// otam_tile (otam_tile.h: otam_gallery_kernel in gallery.hip, otam_indexed_kernel in live.hip), so equal distance blocks give bit-equal
+// results in all of them.
 #pragma once
 #include <hip/hip_runtime.h>
 

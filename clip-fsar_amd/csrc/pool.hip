@@ -4,9 +4,7 @@
 // Copy kernels: one WAVE per destination row.  The row number is wave-uniform, so the search over the table's prefix offsets runs once
 // per row on scalar values (the table loads are scalar loads) and the lanes then stride over the row's 16-byte pieces.
 // A library of its own: the other four keep their pinned export sets.
-#include <stdint.h>
-#include <string.h>
-
+#include "ring_rows.h"
 #include "side_lib.h"
 #include "../../include/clipfsar_pool.h"
 
@@ -15,12 +13,7 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int WAVE = 64;
 constexpr int WAVES = THREADS / WAVE;
-constexpr unsigned MAX_BLOCKS = 4096;          // grid-stride beyond, as stream.hip
 constexpr int COLS = CFSP_TABLE_COLS;
-
-// a row piece: 16 bytes when the rows allow it, 4 otherwise
-template <bool VEC> struct Piece { typedef float type; };
-template <> struct Piece<true> { typedef float4 type; };
 
 // the last table row whose prefix offset in column `col` is <= r (offsets start at 0 and never decrease; rows with a count of 0 share
 // their offset with the row after them and are passed over).  Everything here is wave-uniform.
@@ -74,7 +67,7 @@ __global__ __launch_bounds__(THREADS) void pool_window_sequences_kernel(const fl
     }
 }
 
-// ---- smoothing.  One thread per (table row, c), sequential in k: the arithmetic of stream.hip's smooth_logits_kernel, step for step
+// ---- smoothing.  One thread per (table row, c): smooth_run (ring_rows.h), as stream.hip's smooth_logits_kernel
 __global__ __launch_bounds__(THREADS) void pool_smooth_logits_kernel(const float* logits, float* __restrict__ state, float* out,
                                                                      const int* __restrict__ table, unsigned SC, unsigned C, float alpha) {
     const float om = __fsub_rn(1.0f, alpha);
@@ -83,28 +76,10 @@ __global__ __launch_bounds__(THREADS) void pool_smooth_logits_kernel(const float
         const int* d = table + s * COLS;
         const unsigned nW = (unsigned)d[CFSP_NW];
         if (nW == 0) continue;                                                 // the session's state stays as it is
-        const bool have_state = d[CFSP_HAS_STATE] != 0;
-        const float* x = logits + (size_t)d[CFSP_WIN_OFF] * C + c;
-        float* o = out + (size_t)d[CFSP_WIN_OFF] * C + c;
-        float* st = state + (size_t)d[CFSP_SLOT] * C + c;
-        float y = have_state ? *st : 0.f;
-        for (unsigned k = 0; k < nW; ++k) {
-            const float xk = x[(size_t)k * C];
-            y = (k == 0 && !have_state) ? xk : __fmaf_rn(alpha, y, __fmul_rn(om, xk));
-            o[(size_t)k * C] = y;                                              // out may be logits: this thread alone touches the element
-        }
-        *st = y;
+        const size_t at = (size_t)d[CFSP_WIN_OFF] * C + c;
+        smooth_run(logits + at, out + at, state + (size_t)d[CFSP_SLOT] * C + c, nW, C, alpha, om, d[CFSP_HAS_STATE] != 0);
     }
 }
-
-unsigned blocks_for(long long items, int per_block) {
-    const long long b = (items + per_block - 1) / per_block;
-    return (unsigned)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
-}
-
-bool vec_ok(const void* a, const void* b, int E) { return E % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
-
-constexpr long long MAX_ITEMS = 0x7fffffffLL;   // the kernels index rows, row pieces and windows with 32 bits
 
 // The host copy of the table, before any device work.  cap == 0: ring positions are only required to be non-negative (the smoothing call
 // has no ring); N / NW < 0: that total is not checked.
@@ -112,15 +87,14 @@ int check_table(const char* what, const int32_t* t, int S, int max_streams, int 
     SIDE_REQUIRE(max_streams >= 1 && max_streams <= CFSP_MAX_STREAMS, "%s: max_streams=%d outside 1 .. %d", what, max_streams,
                  CFSP_MAX_STREAMS);
     SIDE_REQUIRE(S >= 1 && S <= max_streams, "%s: a table of S=%d rows for max_streams=%d", what, S, max_streams);
-    thread_local uint64_t seen[CFSP_MAX_STREAMS / 64];
-    memset(seen, 0, sizeof(uint64_t) * (size_t)((max_streams + 63) / 64));
+    SlotBits seen(max_streams);
+    SIDE_REQUIRE(seen.ok(), "%s: out of host memory for %d slots", what, max_streams);
     long long feat = 0, win = 0;
     for (int s = 0; s < S; ++s) {
         const int32_t* d = t + (size_t)s * COLS;
         const int slot = d[CFSP_SLOT];
         SIDE_REQUIRE(slot >= 0 && slot < max_streams, "%s: row %d has slot %d outside 0 .. %d", what, s, slot, max_streams - 1);
-        SIDE_REQUIRE(!(seen[slot >> 6] >> (slot & 63) & 1), "%s: slot %d appears twice in the table (row %d)", what, slot, s);
-        seen[slot >> 6] |= (uint64_t)1 << (slot & 63);
+        SIDE_REQUIRE(!seen.test_and_set(slot), "%s: slot %d appears twice in the table (row %d)", what, slot, s);
         SIDE_REQUIRE(d[CFSP_N] >= 0 && d[CFSP_NW] >= 0, "%s: row %d has a negative count (n=%d nW=%d)", what, s, d[CFSP_N], d[CFSP_NW]);
         SIDE_REQUIRE(d[CFSP_PUT_POS] >= 0 && d[CFSP_WIN_POS] >= 0 && (cap == 0 || (d[CFSP_PUT_POS] < cap && d[CFSP_WIN_POS] < cap)),
                      "%s: row %d has a ring position outside 0 .. cap-1 (put_pos=%d win_pos=%d cap=%d)", what, s, d[CFSP_PUT_POS],

@@ -2,19 +2,13 @@
 // the gather of sliding windows out of it into context2's input, and the smoothing recurrence over consecutive windows.
 // Copy and stream kernels: HBM- and latency-bound, one launch per call, 16-byte accesses where the rows allow them.
 // A library of its own: libclipfsar_hip.so, libclipfsar_gallery.so and libclipfsar_gallery_text.so keep their pinned export sets.
-#include <stdint.h>
-
+#include "ring_rows.h"
 #include "side_lib.h"
 #include "../../include/clipfsar_stream.h"
 
 namespace {
 
 constexpr int THREADS = 256;
-constexpr unsigned MAX_BLOCKS = 4096;          // grid-stride beyond: 16 workgroups per CU of rows in flight is past what HBM needs
-
-// a row piece: 16 bytes when the rows allow it, 4 otherwise
-template <bool VEC> struct Piece { typedef float type; };
-template <> struct Piece<true> { typedef float4 type; };
 
 // ---- ring write.  One thread per row piece: idx -> (b, i, piece); the slot of frame i is first_slot + i, wrapped once (n <= cap)
 template <bool VEC>
@@ -50,32 +44,16 @@ __global__ __launch_bounds__(THREADS) void window_sequences_kernel(const float* 
     }
 }
 
-// ---- smoothing.  One thread per (b, c), sequential in k.  1 - alpha and (1 - alpha) * x are rounded to fp32, then ONE fma per step
+// ---- smoothing.  One thread per (b, c): smooth_run (ring_rows.h)
 __global__ __launch_bounds__(THREADS) void smooth_logits_kernel(const float* logits, float* __restrict__ state, float* out, unsigned BC,
                                                                 unsigned nW, unsigned C, float alpha, int have_state) {
     const float om = __fsub_rn(1.0f, alpha);
     for (unsigned idx = blockIdx.x * THREADS + threadIdx.x; idx < BC; idx += gridDim.x * THREADS) {
         const unsigned b = idx / C, c = idx - b * C;
-        const float* x = logits + (size_t)b * nW * C + c;
-        float* o = out + (size_t)b * nW * C + c;
-        float y = have_state ? state[idx] : 0.f;
-        for (unsigned k = 0; k < nW; ++k) {
-            const float xk = x[(size_t)k * C];
-            y = (k == 0 && !have_state) ? xk : __fmaf_rn(alpha, y, __fmul_rn(om, xk));
-            o[(size_t)k * C] = y;                                          // out may be logits: this thread alone touches the element
-        }
-        state[idx] = y;
+        const size_t at = (size_t)b * nW * C + c;
+        smooth_run(logits + at, out + at, state + idx, nW, C, alpha, om, have_state);
     }
 }
-
-unsigned blocks_for(long long total) {
-    const long long b = (total + THREADS - 1) / THREADS;
-    return (unsigned)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
-}
-
-bool vec_ok(const void* a, const void* b, int E) { return E % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
-
-constexpr long long MAX_ITEMS = 0x7fffffffLL;   // the kernels index row pieces with 32 bits
 
 }  // namespace
 
@@ -95,11 +73,11 @@ extern "C" int cfss_ring_put(const float* feats, float* ring, int B, int n, int 
     const unsigned first_slot = (unsigned)(first_frame % cap);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (vec)
-        hipLaunchKernelGGL(ring_put_kernel<true>, dim3(blocks_for(total)), dim3(THREADS), 0, s, feats, ring, (unsigned)total, (unsigned)n,
-                           (unsigned)pieces, (unsigned)cap, first_slot);
+        hipLaunchKernelGGL(ring_put_kernel<true>, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, s, feats, ring, (unsigned)total,
+                           (unsigned)n, (unsigned)pieces, (unsigned)cap, first_slot);
     else
-        hipLaunchKernelGGL(ring_put_kernel<false>, dim3(blocks_for(total)), dim3(THREADS), 0, s, feats, ring, (unsigned)total, (unsigned)n,
-                           (unsigned)pieces, (unsigned)cap, first_slot);
+        hipLaunchKernelGGL(ring_put_kernel<false>, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, s, feats, ring, (unsigned)total,
+                           (unsigned)n, (unsigned)pieces, (unsigned)cap, first_slot);
     return check_launch("cfss_ring_put");
 }
 
@@ -129,10 +107,10 @@ extern "C" int cfss_window_sequences(const float* ring, float* X, int B, int nW,
     const unsigned base_slot = (unsigned)(lo % cap);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (vec)
-        hipLaunchKernelGGL(window_sequences_kernel<true>, dim3(blocks_for(total)), dim3(THREADS), 0, s, ring, X, (unsigned)total,
+        hipLaunchKernelGGL(window_sequences_kernel<true>, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, s, ring, X, (unsigned)total,
                            (unsigned)nW, (unsigned)T, (unsigned)pieces, (unsigned)cap, (unsigned)stride, (unsigned)rate, base_slot);
     else
-        hipLaunchKernelGGL(window_sequences_kernel<false>, dim3(blocks_for(total)), dim3(THREADS), 0, s, ring, X, (unsigned)total,
+        hipLaunchKernelGGL(window_sequences_kernel<false>, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, s, ring, X, (unsigned)total,
                            (unsigned)nW, (unsigned)T, (unsigned)pieces, (unsigned)cap, (unsigned)stride, (unsigned)rate, base_slot);
     return check_launch("cfss_window_sequences");
 }
@@ -144,7 +122,8 @@ extern "C" int cfss_smooth_logits(const float* logits, float* state, float* out,
     SIDE_REQUIRE(alpha >= 0.0f && alpha < 1.0f, "cfss_smooth_logits: alpha=%g outside [0, 1)", (double)alpha);
     SIDE_REQUIRE(windows_seen >= 0, "cfss_smooth_logits: windows_seen=%lld is negative", (long long)windows_seen);
     SIDE_REQUIRE((long long)B * C <= MAX_ITEMS, "cfss_smooth_logits: too large for one launch (B=%d C=%d)", B, C);
-    hipLaunchKernelGGL(smooth_logits_kernel, dim3(blocks_for((long long)B * C)), dim3(THREADS), 0, static_cast<hipStream_t>(stream),
-                       logits, state, out, (unsigned)B * (unsigned)C, (unsigned)nW, (unsigned)C, alpha, windows_seen > 0 ? 1 : 0);
+    hipLaunchKernelGGL(smooth_logits_kernel, dim3(blocks_for((long long)B * C, THREADS)), dim3(THREADS), 0,
+                       static_cast<hipStream_t>(stream), logits, state, out, (unsigned)B * (unsigned)C, (unsigned)nW, (unsigned)C, alpha,
+                       windows_seen > 0 ? 1 : 0);
     return check_launch("cfss_smooth_logits");
 }

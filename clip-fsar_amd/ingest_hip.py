@@ -15,7 +15,7 @@ import os
 import torch  # noqa: F401  (imported first so that torch's HIP runtime is the one the library binds to)
 
 from . import _cabi, hip
-from .pool_hip import Table, TableUploader
+from .pool_hip import TableUploader
 
 ABI_VERSION = 1          # CFSI_ABI_VERSION of include/clipfsar_ingest.h this file's SIGNATURES were written against
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libclipfsar_ingest.so")
@@ -54,10 +54,7 @@ def table_uploader(device, max_rows, depth=4):
 
 
 def _table(t):
-    if not isinstance(t, Table) or t.host.is_cuda or t.host.dtype != torch.int32 or tuple(t.host.shape) != (t.S, TABLE_COLS) \
-            or not t.host.is_contiguous() or tuple(t.dev.shape) != (t.S, TABLE_COLS):
-        raise RuntimeError("clip_fsar_amd.ingest_hip: table must be a Table of [S, %d] int32 host rows and their device copy" % TABLE_COLS)
-    return ctypes.c_void_p(t.host.data_ptr()), _dev(t.dev, torch.int32, "table"), t.S
+    return _cabi.table_args(t, TABLE_COLS, "ingest_hip")
 
 
 def transform_frames(src, out, table, crop, mean, std):

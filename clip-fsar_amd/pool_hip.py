@@ -10,7 +10,6 @@ copy, so a buffer is rewritten only once the copy that read it has completed and
 """
 from __future__ import annotations
 
-import collections
 import ctypes
 import os
 
@@ -50,7 +49,7 @@ _check = _cabi.checker(lib, "cfsp_")
 _shape = _cabi.shape_checker("pool_hip")
 _dev, _stream = hip._dev, hip._stream
 
-Table = collections.namedtuple("Table", "host dev S")          # host: pinned [S, 8] int32 rows; dev: their device copy
+Table = _cabi.Table
 
 
 class TableUploader:
@@ -88,10 +87,7 @@ class TableUploader:
 
 
 def _table(t):
-    if not isinstance(t, Table) or t.host.is_cuda or t.host.dtype != torch.int32 or tuple(t.host.shape) != (t.S, TABLE_COLS) \
-            or not t.host.is_contiguous() or tuple(t.dev.shape) != (t.S, TABLE_COLS):
-        raise RuntimeError("clip_fsar_amd.pool_hip: table must be a Table of [S, %d] int32 host rows and their device copy" % TABLE_COLS)
-    return ctypes.c_void_p(t.host.data_ptr()), _dev(t.dev, torch.int32, "table"), t.S
+    return _cabi.table_args(t, TABLE_COLS, "pool_hip")
 
 
 def ring_put(feats, ring, table):

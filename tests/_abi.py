@@ -1,5 +1,5 @@
-"""What the three ABI tests (test_abi, test_gallery_abi, test_gallery_text_abi) share: the prototypes a C header declares and the symbols a
-built library exports."""
+"""What the ABI tests (test_abi, test_<side library>_abi) share: the prototypes a C header declares, the symbols a built library exports
+and the resource reports of the other libraries."""
 import re
 import subprocess
 
@@ -19,3 +19,11 @@ def _exported(lib_path):
     out = subprocess.run(["nm", "-D", "--defined-only", lib_path], stdout=subprocess.PIPE, text=True, check=True).stdout
     syms = {l.split()[-1] for l in out.splitlines() if l.strip()}
     return {s for s in syms if not s.startswith(("__hip", "_init", "_fini", "__bss", "_edata", "_end"))}
+
+
+def _other_reports(name):
+    """the resource reports of the product library and of every side library but `name`"""
+    from clip_fsar_amd import build as b
+    others = [b.USAGE] + [b.SIDE_LIBS[n].usage for n in b.side_lib_names() if n != name]
+    assert len(others) == 6 and b.SIDE_LIBS[name].usage not in others
+    return others

@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_gallery.h")
@@ -84,8 +84,9 @@ def test_gallery_kernels_use_no_scratch_and_stay_out_of_the_product_report(glib)
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0, (n, u)
     assert b.SIDE_LIBS["gallery"].source not in b.SOURCES and b.SIDE_LIBS["gallery"].usage != b.USAGE
-    if os.path.exists(b.USAGE):
-        assert not any("otam_gallery_kernel" in n for n in json.load(open(b.USAGE)))
+    for other in _other_reports("gallery"):
+        if os.path.exists(other):
+            assert not any("otam_gallery_kernel" in n for n in json.load(open(other))) and not set(usage) & set(json.load(open(other))), other
 
 
 def test_gallery_refuses_text_modes_without_gpu():

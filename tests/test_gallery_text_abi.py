@@ -9,7 +9,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_gallery_text.h")
@@ -96,31 +96,9 @@ def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(tlib):
         assert u.get("scratch", 0) == 0, (n, u)
         assert "otam_gallery_kernel" not in n, n
     assert b.SIDE_LIBS["gallery_text"].source not in b.SOURCES
-    assert len({b.SIDE_LIBS["gallery_text"].usage, b.SIDE_LIBS["gallery"].usage, b.USAGE}) == 3
-    for other in (b.USAGE, b.SIDE_LIBS["gallery"].usage):
+    for other in _other_reports("gallery_text"):
         if os.path.exists(other):
             assert not set(usage) & set(json.load(open(other)))
-
-
-def test_product_staleness_ignores_the_text_gallery_source(monkeypatch):
-    """editing csrc/gallery_text.hip rebuilds the text library only: libclipfsar_hip.so's staleness check skips it; a shared header
-    rebuilds exactly the libraries whose sources include it"""
-    from clip_fsar_amd import build as b
-    g, t = b.SIDE_LIBS["gallery"], b.SIDE_LIBS["gallery_text"]
-
-    def stale_after_editing(name):               # (product, gallery, text gallery) with csrc/<name> newer than every library
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
-        return b._stale(b.LIB, b._product_deps()), b._stale(g.lib, b._side_deps("gallery")), b._stale(t.lib, b._side_deps("gallery_text"))
-
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    assert stale_after_editing(t.source) == (False, False, True)
-    assert stale_after_editing(g.source) == (False, True, False)
-    assert stale_after_editing("fp32_tile_gemm.h") == (False, True, True)
-    assert stale_after_editing("side_lib.h") == (False, True, True)
-    assert stale_after_editing("otam_dp.h") == (True, True, False)
-    assert stale_after_editing("common.h") == (True, True, True)
-    assert stale_after_editing("tail.hip") == (True, False, False)
-    assert stale_after_editing("clipfsar_gallery_text.h") == (False, False, True)
 
 
 # ------------------------------------------------------------------ mode resolution (no GPU: a stub head)

@@ -9,7 +9,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_ingest.h")
@@ -56,48 +56,16 @@ def test_abi_version_is_checked_at_load(ilib, monkeypatch):
 
 
 def test_the_other_five_libraries_export_nothing_of_it(ilib):
-    from clip_fsar_amd import build as b
     from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, ingest_hip, pool_hip, stream_hip
     ours = _exported(ingest_hip.LIB_PATH)
     assert not any(s.startswith(("cfsg_", "cfsar_", "cfgt_", "cfss_", "cfsp_")) for s in ours)
     for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip):
         assert not any(s.startswith("cfsi_") for s in _exported(mod.LIB_PATH)), mod.__name__
-    # the pinned lists of the older tests stay; the sixth library is named by all_side_lib_names() alone
-    assert list(b.SIDE_LIBS) == ["gallery", "gallery_text", "stream"] and list(b.MORE_SIDE_LIBS) == ["pool"]
-    assert b.side_lib_names() == ["gallery", "gallery_text", "stream", "pool"]
-    assert b.all_side_lib_names() == b.side_lib_names() + ["ingest"]
-    assert b.side_lib("ingest").source == "ingest.hip" and b.side_lib("pool") is b.MORE_SIDE_LIBS["pool"]
-
-
-def test_staleness_with_six_libraries(monkeypatch):
-    """editing csrc/ingest.hip or include/clipfsar_ingest.h rebuilds the ingest library only; the transform header shared with rowops.hip
-    rebuilds the product library and the ingest library"""
-    from clip_fsar_amd import build as b
-
-    def stale_after_editing(name):               # (product, gallery, text gallery, stream, pool, ingest) with <name> newer than every library
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
-        return (b._stale(b.LIB, b._product_deps()),) + tuple(b._stale(b.side_lib(n).lib, b._side_deps(n)) for n in b.all_side_lib_names())
-
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    assert stale_after_editing("ingest.hip") == (False, False, False, False, False, True)
-    assert stale_after_editing("clipfsar_ingest.h") == (False, False, False, False, False, True)
-    assert stale_after_editing("frame_transform.h") == (True, False, False, False, False, True)
-    assert stale_after_editing("rowops.hip") == (True, False, False, False, False, False)
-    assert stale_after_editing("pool.hip") == (False, False, False, False, True, False)
-    assert stale_after_editing("side_lib.h") == (False, True, True, True, True, True)
-    assert stale_after_editing("common.h") == (True, True, True, True, True, True)
-    deps = b._product_deps()
-    assert os.path.join(b.CSRC, "ingest.hip") not in deps and os.path.join(b.CSRC, "frame_transform.h") in deps
-    assert os.path.join(b.CSRC, "frame_transform.h") in b._side_deps("ingest")
-    for src in ("rowops.hip", "ingest.hip"):      # both kernels compile the arithmetic from the one header
-        text = open(os.path.join(b.CSRC, src)).read()
-        assert '#include "frame_transform.h"' in text and "frame_transform_pixel(" in text, src
-        assert "inv255" not in text, src
 
 
 def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(ilib):
     from clip_fsar_amd import build as b
-    sl = b.side_lib("ingest")
+    sl = b.SIDE_LIBS["ingest"]
     if not os.path.exists(sl.usage):
         b.build_side("ingest", force=True, verbose=False)
     usage = json.load(open(sl.usage))
@@ -106,8 +74,7 @@ def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(ilib):
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
     assert sl.source not in b.SOURCES
-    others = [b.USAGE] + [b.side_lib(n).usage for n in b.side_lib_names()]
-    assert len(set(others + [sl.usage])) == 6
+    others = _other_reports("ingest")
     assert os.path.normpath(sl.usage).endswith(os.path.join("build", "ingest", "resource_usage.json"))
     for other in others:
         if os.path.exists(other):
@@ -118,7 +85,7 @@ def test_build_products_are_git_ignored():
     from clip_fsar_amd import build as b
     patterns = set(open(os.path.join(ROOT, ".gitignore")).read().split())
     assert {"*.so", "*.o", "build/"} <= patterns
-    sl = b.side_lib("ingest")
+    sl = b.SIDE_LIBS["ingest"]
     assert sl.lib.endswith(os.sep + "libclipfsar_ingest.so") and os.sep + "build" + os.sep in sl.usage
 
 

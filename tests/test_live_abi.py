@@ -10,7 +10,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_live.h")
@@ -57,54 +57,16 @@ def test_abi_version_is_checked_at_load(llib, monkeypatch):
 
 
 def test_the_other_six_libraries_export_nothing_of_it(llib):
-    from clip_fsar_amd import build as b
     from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, ingest_hip, live_hip, pool_hip, stream_hip
     ours = _exported(live_hip.LIB_PATH)
     assert ours and all(s.startswith("cfsl_") for s in ours), sorted(ours)
     for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip):
         assert not any(s.startswith("cfsl_") for s in _exported(mod.LIB_PATH)), mod.__name__
-    # the pinned tables and name functions of the older tests stay; the seventh library is named by every_side_lib_names() alone
-    assert list(b.SIDE_LIBS) == ["gallery", "gallery_text", "stream"] and list(b.MORE_SIDE_LIBS) == ["pool"]
-    assert list(b.INGEST_SIDE_LIBS) == ["ingest"] and list(b.LIVE_SIDE_LIBS) == ["live"]
-    assert b.side_lib_names() == ["gallery", "gallery_text", "stream", "pool"]
-    assert b.all_side_lib_names() == b.side_lib_names() + ["ingest"]
-    assert b.every_side_lib_names() == ["gallery", "gallery_text", "stream", "pool", "ingest", "live"]
-    assert len([b.LIB] + [b.side_lib(n).lib for n in b.every_side_lib_names()]) == 7
-    assert b.side_lib("live").source == "live.hip" and b.side_lib("live") is b.LIVE_SIDE_LIBS["live"]
-    assert b.side_lib("ingest") is b.INGEST_SIDE_LIBS["ingest"] and b.side_lib("pool") is b.MORE_SIDE_LIBS["pool"]
-
-
-def test_staleness_with_seven_libraries(monkeypatch):
-    """editing csrc/live.hip or include/clipfsar_live.h rebuilds the live library only; the tile GEMM header rebuilds the two gallery
-    libraries and this one, the OTAM DP header the product library, the gallery and this one"""
-    from clip_fsar_amd import build as b
-
-    def stale_after_editing(name):               # (product, gallery, text gallery, stream, pool, ingest, live)
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
-        return (b._stale(b.LIB, b._product_deps()),) + tuple(b._stale(b.side_lib(n).lib, b._side_deps(n)) for n in b.every_side_lib_names())
-
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    assert stale_after_editing("live.hip") == (False, False, False, False, False, False, True)
-    assert stale_after_editing("clipfsar_live.h") == (False, False, False, False, False, False, True)
-    assert stale_after_editing("fp32_tile_gemm.h") == (False, True, True, False, False, False, True)
-    assert stale_after_editing("otam_dp.h") == (True, True, False, False, False, False, True)
-    assert stale_after_editing("gallery.hip") == (False, True, False, False, False, False, False)
-    assert stale_after_editing("side_lib.h") == (False, True, True, True, True, True, True)
-    assert stale_after_editing("common.h") == (True,) * 7
-    deps = b._product_deps()
-    assert os.path.join(b.CSRC, "live.hip") not in deps and os.path.join(b.CSRC, "otam_dp.h") in deps
-    assert os.path.join(b.CSRC, "fp32_tile_gemm.h") not in deps
-    # one K loop: the dense kernels and the indexed kernel call the same function of the one header, the dense ones through the identity map
-    header = open(os.path.join(b.CSRC, "fp32_tile_gemm.h")).read()
-    assert header.count("__builtin_amdgcn_mfma_f32_16x16x4f32") == 1
-    assert "fp32_tile_gemm_rows(" in open(os.path.join(b.CSRC, "live.hip")).read()
-    for src in ("gallery.hip", "gallery_text.hip"):
-        assert "fp32_tile_gemm(" in open(os.path.join(b.CSRC, src)).read(), src
 
 
 def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(llib):
     from clip_fsar_amd import build as b
-    sl = b.side_lib("live")
+    sl = b.SIDE_LIBS["live"]
     if not os.path.exists(sl.usage):
         b.build_side("live", force=True, verbose=False)
     usage = json.load(open(sl.usage))
@@ -114,8 +76,7 @@ def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(llib):
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
     assert sl.source not in b.SOURCES
-    others = [b.USAGE] + [b.side_lib(n).usage for n in b.all_side_lib_names()]
-    assert len(set(others + [sl.usage])) == 7
+    others = _other_reports("live")
     assert os.path.normpath(sl.usage).endswith(os.path.join("build", "live", "resource_usage.json"))
     for other in others:
         if os.path.exists(other):

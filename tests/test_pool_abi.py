@@ -10,7 +10,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_pool.h")
@@ -47,7 +47,6 @@ def test_header_exported_exactly_and_arity_matches(plib):
 
 
 def test_other_libraries_keep_their_export_sets(plib):
-    from clip_fsar_amd import build as b
     from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, pool_hip, stream_hip
     ours = _exported(pool_hip.LIB_PATH)
     assert not any(s.startswith(("cfsg_", "cfsar_", "cfgt_", "cfss_")) for s in ours)
@@ -61,27 +60,6 @@ def test_other_libraries_keep_their_export_sets(plib):
         if mod is hip and os.environ.get("CFSAR_DEV", "0") == "1":
             continue                              # a developer build of the product library exports its debug hooks too
         assert syms == set(protos), (mod.__name__, sorted(syms ^ set(protos)))
-    assert list(b.SIDE_LIBS) == ["gallery", "gallery_text", "stream"] and list(b.MORE_SIDE_LIBS) == ["pool"]
-    assert b.side_lib_names() == ["gallery", "gallery_text", "stream", "pool"]
-
-
-def test_staleness_with_five_libraries(monkeypatch):
-    """editing csrc/pool.hip or include/clipfsar_pool.h rebuilds the pool library only; the shared headers reach it too"""
-    from clip_fsar_amd import build as b
-
-    def stale_after_editing(name):               # (product, gallery, text gallery, stream, pool) with <name> newer than every library
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
-        return (b._stale(b.LIB, b._product_deps()),) + tuple(b._stale(b.side_lib(n).lib, b._side_deps(n)) for n in b.side_lib_names())
-
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    assert stale_after_editing("pool.hip") == (False, False, False, False, True)
-    assert stale_after_editing("clipfsar_pool.h") == (False, False, False, False, True)
-    assert stale_after_editing("stream.hip") == (False, False, False, True, False)
-    assert stale_after_editing("clipfsar_stream.h") == (False, False, False, True, False)
-    assert stale_after_editing("side_lib.h") == (False, True, True, True, True)
-    assert stale_after_editing("common.h") == (True, True, True, True, True)
-    assert stale_after_editing("tail.hip") == (True, False, False, False, False)
-    assert os.path.join(b.CSRC, "pool.hip") not in b._product_deps()
 
 
 # ------------------------------------------------------------------ validation, without a GPU
@@ -196,7 +174,7 @@ def test_python_wrappers_reject_cpu_tensors_and_bad_tables(plib):
 
 def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(plib):
     from clip_fsar_amd import build as b
-    sl = b.side_lib("pool")
+    sl = b.SIDE_LIBS["pool"]
     if not os.path.exists(sl.usage):
         b.build_side("pool", force=True, verbose=False)
     usage = json.load(open(sl.usage))
@@ -207,8 +185,7 @@ def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(plib):
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
     assert sl.source == "pool.hip" and sl.source not in b.SOURCES
-    others = [b.USAGE] + [b.SIDE_LIBS[n].usage for n in b.SIDE_LIBS]
-    assert len(set(others + [sl.usage])) == 5
+    others = _other_reports("pool")
     assert os.path.normpath(sl.usage).endswith(os.path.join("build", "pool", "resource_usage.json"))
     for other in others:
         if os.path.exists(other):
@@ -220,7 +197,7 @@ def test_build_products_are_git_ignored():
     from clip_fsar_amd import build as b
     patterns = set(open(os.path.join(ROOT, ".gitignore")).read().split())
     assert {"*.so", "*.o", "build/"} <= patterns
-    sl = b.side_lib("pool")
+    sl = b.SIDE_LIBS["pool"]
     assert sl.lib.endswith(".so") and os.sep + "build" + os.sep in sl.usage
 
 

@@ -10,7 +10,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _exported, _other_reports, _prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_stream.h")
@@ -128,36 +128,11 @@ def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(slib):
     for n, u in usage.items():
         assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
     assert sl.source == "stream.hip" and sl.source not in b.SOURCES
-    others = [b.USAGE] + [b.SIDE_LIBS[n].usage for n in ("gallery", "gallery_text")]
-    assert len(set(others + [sl.usage])) == 4
+    others = _other_reports("stream")
     assert os.path.normpath(sl.usage).endswith(os.path.join("build", "stream", "resource_usage.json"))
     for other in others:
         if os.path.exists(other):
             assert not set(usage) & set(json.load(open(other))), other
-
-
-def test_staleness_with_four_libraries(monkeypatch):
-    """editing csrc/stream.hip or include/clipfsar_stream.h rebuilds the stream library only; what
-    test_product_staleness_ignores_the_text_gallery_source expects of the other three holds beside it"""
-    from clip_fsar_amd import build as b
-    assert list(b.SIDE_LIBS) == ["gallery", "gallery_text", "stream"]
-
-    def stale_after_editing(name):               # (product, gallery, text gallery, stream) with <name> newer than every library
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + name) else 1.0)
-        return (b._stale(b.LIB, b._product_deps()),) + tuple(b._stale(b.SIDE_LIBS[n].lib, b._side_deps(n)) for n in b.SIDE_LIBS)
-
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    assert stale_after_editing("stream.hip") == (False, False, False, True)
-    assert stale_after_editing("clipfsar_stream.h") == (False, False, False, True)
-    assert stale_after_editing("gallery_text.hip") == (False, False, True, False)
-    assert stale_after_editing("gallery.hip") == (False, True, False, False)
-    assert stale_after_editing("fp32_tile_gemm.h") == (False, True, True, False)
-    assert stale_after_editing("side_lib.h") == (False, True, True, True)
-    assert stale_after_editing("otam_dp.h") == (True, True, False, False)
-    assert stale_after_editing("common.h") == (True, True, True, True)
-    assert stale_after_editing("tail.hip") == (True, False, False, False)
-    assert stale_after_editing("clipfsar_gallery_text.h") == (False, False, True, False)
-    assert stale_after_editing("clipfsar_gallery.h") == (False, True, False, False)
 
 
 # ------------------------------------------------------------------ the host plan
