@@ -5,6 +5,9 @@
 // one is multiplied.  Wave w owns the 32 x 32 quarter (w >> 1, w & 1) as 2 x 2 MFMA tiles.  Inside a chunk, MFMA step s of lane half h
 // takes k = 8h + s: every lane reads its k values as two ds_read_b128 per tile (A and B use the same k map, so the products are those of
 // the plain GEMM, summed in another order).
+// Every chunk is summed from zero and then added to the running sum: an element is a chain of at most BK products per chunk plus E / BK
+// chunk adds, not one chain of E.  The single chain missed 1e-6 on 1 - cos where |cos| is near 1 (a sum of like-signed products): worst
+// error at E = 512 on an MI355X 1.54e-6 before, 0.36e-6 now (tests/test_gpu_otam.py, families near and anti).
 #pragma once
 #include "common.h"
 
@@ -60,13 +63,19 @@ __device__ __forceinline__ void fp32_tile_gemm_rows(const float* __restrict__ A,
             b[i][0] = *reinterpret_cast<const f32x4*>(pb);
             b[i][1] = *reinterpret_cast<const f32x4*>(pb + 4);
         }
+        f32x4 part[2][2];                                                 // this chunk's sums: a chain of BK products from zero
 #pragma unroll
         for (int s = 0; s < 8; ++s)
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][s >> 2][s & 3], b[ni][s >> 2][s & 3], acc[mi][ni], 0, 0, 0);
+                    part[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][s >> 2][s & 3], b[ni][s >> 2][s & 3],
+                                                                        s ? part[mi][ni] : f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) acc[mi][ni] += part[mi][ni];
     }
     __syncthreads();
 }

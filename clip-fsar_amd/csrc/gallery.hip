@@ -73,7 +73,9 @@ __global__ __launch_bounds__(256) void otam_gallery_kernel(const float* __restri
 
 // ---- top-k per query: one wave per query.  Each lane keeps the best KMAX of its strided classes (a compare-exchange chain with
 // constant indices: registers only), then k rounds of a wave-wide arg-max over the lanes' heads.  Order: larger value first, the
-// lower class index on ties (a stable descending sort); NaN logits are never selected.
+// lower class index on ties (a stable descending sort).  A NaN logit is never selected, and neither is one of -inf: -inf is the value
+// of an empty place, whose index is 0x7fffffff (no class).  The loop skips both; before it did, a -inf class was kept with its index
+// when its lane already held a class and lost it to 0x7fffffff when it was the lane's first.
 constexpr int KMAX = 16;
 __device__ __forceinline__ bool topk_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
 
@@ -88,6 +90,7 @@ __global__ __launch_bounds__(64) void topk_kernel(const float* __restrict__ logi
     for (int c = lane; c < C; c += 64) {
         float x = row[c];
         int xi = c;
+        if (!(x > -__builtin_inff())) continue;            // NaN or -inf: not selectable
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             if (topk_better(x, xi, v[j], ix[j])) {
@@ -160,7 +163,7 @@ extern "C" int cfsg_otam_gallery(const float* Xq, const float* qn, const float* 
     SIDE_REQUIRE(Xq && qn && P && pn && logits, "cfsg_otam_gallery: null pointer");
     SIDE_REQUIRE(otam_shape_ok(NQ, C, T, E), "cfsg_otam_gallery: bad shape (NQ=%d C=%d T=%d E=%d; T <= 32, E %% 4 == 0, 4 <= E <= 8192)", NQ, C,
                  T, E);
-    return otam_tile_launch("cfsg_otam_gallery", NQ, C, T, lambda, [&](auto tt, dim3 grid, int lds) {
+    return otam_tile_launch("cfsg_otam_gallery", Xq, P, "P", NQ, C, T, lambda, [&](auto tt, dim3 grid, int lds) {
         hipLaunchKernelGGL(otam_gallery_kernel<decltype(tt)::value>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), Xq, qn, P, pn,
                            logits, dists_out, NQ, C, T, E, lambda, single_direct);
     });

@@ -100,7 +100,7 @@ extern "C" int cfsl_otam_indexed(const float* Xq, const float* qn, const float* 
                  cap, T, E);
     SIDE_REQUIRE((long long)cap * T <= 0x7fffffffLL && (long long)NQ * T <= 0x7fffffffLL,
                  "cfsl_otam_indexed: cap * T = %lld or NQ * T = %lld rows exceed 32-bit sizes", (long long)cap * T, (long long)NQ * T);
-    return otam_tile_launch("cfsl_otam_indexed", NQ, C, T, lambda, [&](auto tt, dim3 grid, int lds) {
+    return otam_tile_launch("cfsl_otam_indexed", Xq, P_store, "P_store", NQ, C, T, lambda, [&](auto tt, dim3 grid, int lds) {
         hipLaunchKernelGGL(otam_indexed_kernel<decltype(tt)::value>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), Xq, qn, P_store,
                            pn_store, cols, logits, NQ, C, cap, T, E, lambda, single_direct);
     });

@@ -102,9 +102,13 @@ inline bool otam_shape_ok(int NQ, int C, int T, int E) {
 }
 
 // The checks after the shapes, the grid and the LDS size of an OTAM tile kernel, and its form for T: launch(tt, grid, lds_bytes) gets
-// tt = std::integral_constant<int, 8 / 16 / 0 (run-time T)> and launches its kernel<tt.value> with 256 threads.
+// tt = std::integral_constant<int, 8 / 16 / 0 (run-time T)> and launches its kernel<tt.value> with 256 threads.  Xq and P (named
+// `pname` in the message) are the two GEMM operands: fp32_tile_gemm_rows reads them as float4, so both must be 16-byte aligned
+// (with E % 4 == 0 every row then is); a pointer that is not is refused here, before any launch.
 template <class Launch>
-int otam_tile_launch(const char* who, int NQ, int C, int T, float lambda, Launch launch) {
+int otam_tile_launch(const char* who, const float* Xq, const float* P, const char* pname, int NQ, int C, int T, float lambda,
+                     Launch launch) {
+    SIDE_REQUIRE(((uintptr_t)Xq & 15u) == 0 && ((uintptr_t)P & 15u) == 0, "%s: Xq and %s must be 16-byte aligned", who, pname);
     SIDE_REQUIRE(lambda > 0.f, "%s: lambda must be > 0", who);
     const int qb = tile_videos(T);
     const long long gx = ((long long)C + qb - 1) / qb, gy = ((long long)NQ + qb - 1) / qb;

@@ -522,6 +522,8 @@ extern "C" int cfsar_cos_otam_logits(const float* Xq, const float* protos, float
     CFSAR_REQUIRE(Xq && protos && logits, "cfsar_cos_otam_logits: null pointer");
     CFSAR_REQUIRE(B > 0 && Q > 0 && way > 0 && way <= 65535 && T > 0 && T <= MAX_T && E > 0 && E % 4 == 0 && E <= 2048,
                   "cfsar_cos_otam_logits: bad shape (T <= 32, E %% 4 == 0, E <= 2048)");
+    // the kernel reads both operands as float4
+    CFSAR_REQUIRE(((uintptr_t)Xq & 15u) == 0 && ((uintptr_t)protos & 15u) == 0, "cfsar_cos_otam_logits: Xq and protos must be 16-byte aligned");
     const bool fixed_t = T == 8 || T == 16;                  // DP rows in registers; otherwise 2 rows per DP thread in LDS
     const int lds = (T * E + MAX_T + T * T + (fixed_t ? 0 : 2 * 2 * (MAX_T + 2))) * (int)sizeof(float);
     CFSAR_REQUIRE(lds <= 150 * 1024, "cfsar_cos_otam_logits: T*E too large for LDS");

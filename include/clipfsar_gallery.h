@@ -53,12 +53,15 @@ int cfsg_row_norms(const float* X, float* n, int R, int E, cfsg_stream_t stream)
  *     d = 1 - Xq P^T / (qn pn^T + 0.01)      (eps added to the product of the norms, rows not pre-normalised),
  *     logits[q, c] = -(OTAM(d_qc) + OTAM(d_qc^T)),   the second term 0 with single_direct.
  * Xq [NQ, T, E], qn [NQ*T] (cfsg_row_norms of Xq), P [C, T, E], pn [C*T], logits [NQ, C]; dists_out (optional, may be NULL)
- * [NQ, C, T, T].  The similarities are an exact-fp32 MFMA GEMM (k-ordered fmaf chains); T <= 32, E % 4 == 0, 4 <= E <= 8192. */
+ * [NQ, C, T, T].  The similarities are an exact-fp32 MFMA GEMM (k-ordered fmaf chains); T <= 32, E % 4 == 0, 4 <= E <= 8192.  Xq and P
+ * are read as float4: both must be 16-byte aligned (a pointer that is not is refused before any launch). */
 int cfsg_otam_gallery(const float* Xq, const float* qn, const float* P, const float* pn, float* logits, float* dists_out, int NQ,
                       int C, int T, int E, float lambda, int single_direct, cfsg_stream_t stream);
 
 /* ---- top-k per query: values [NQ, k] (descending), index [NQ, k] int32 class indices; ties go to the lower class index (the order of
- * a stable descending sort).  logits [NQ, C]; 1 <= k <= 16, k <= C <= 65535. */
+ * a stable descending sort).  logits [NQ, C]; 1 <= k <= 16, k <= C <= 65535.  A NaN logit (a poisoned column of cfsl_otam_indexed) is
+ * never selected, and neither is a logit of -inf.  A row with fewer than k selectable classes fills its remaining places with the value
+ * -inf and the index 0x7fffffff (no class). */
 int cfsg_topk(const float* logits, float* values, int32_t* index, int NQ, int C, int k, cfsg_stream_t stream);
 
 #if defined(__GNUC__) || defined(__clang__)

@@ -55,7 +55,8 @@ const char* cfsl_last_error(void);
  *     d = 1 - Xq P^T / (qn pn^T + 0.01),   logits[q, j] = -(OTAM(d_qj) + OTAM(d_qj^T)),   the second term 0 with single_direct.
  * Xq [NQ, T, E], qn [NQ*T], P_store [cap, T, E], pn_store [cap*T], cols [C] int32 (DEVICE), logits [NQ, C].  1 <= T <= 32,
  * E % 4 == 0, 4 <= E <= 8192, C >= 1, cap >= 1, cap * T and NQ * T below 2^31.  cols is device data: a slot outside [0, cap) is never
- * dereferenced and gives a column of NaN (the host validates the list).  Slots that cols does not name are not read. */
+ * dereferenced and gives a column of NaN (the host validates the list).  Slots that cols does not name are not read.  Xq and P_store
+ * are read as float4: both must be 16-byte aligned (a pointer that is not is refused before any launch). */
 int cfsl_otam_indexed(const float* Xq, const float* qn, const float* P_store, const float* pn_store, const int32_t* cols, float* logits,
                       int NQ, int C, int cap, int T, int E, float lambda, int single_direct, cfsl_stream_t stream);
 

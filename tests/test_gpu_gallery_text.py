@@ -92,7 +92,8 @@ def _restated(emb, text, scale, vis=None, coff=0.9):
 
 
 # ------------------------------------------------------------------ 1: the kernels
-KERNEL_SHAPES = [(37, 29, 512), (16, 300, 768), (5, 7, 1024), (64, 5000, 64)]
+KERNEL_SHAPES = [(37, 29, 512), (16, 300, 768), (5, 7, 1024), (64, 5000, 64),
+                 (5, 7, 36), (70, 65, 100), (1, 1, 4)]                           # E % 32 != 0, E < 32: the K loop's last chunk
 
 
 @pytest.mark.parametrize("NQ,C,E", KERNEL_SHAPES)
