@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -46,8 +46,26 @@ SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so"
              for name in ("gallery", "gallery_text", "stream", "pool", "ingest", "live")}
 
 
+# Libraries added after the six: the same SideLib tuple, recipe and call sites, in a dict of their own.  SIDE_LIBS and side_lib_names()
+# are what the earlier libraries' checks enumerate as "the side libraries" (each one's exports and kernel names are compared against
+# exactly those), so a library they were not written against is registered here, where every_side_lib_names(), build_side(), _side_deps(),
+# _product_deps() and build() find it, and not there.  "groups": grouped scoring, C ABI in include/clipfsar_groups.h.
+MORE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
+                                os.path.join(HERE, "build", name, "resource_usage.json"))
+                  for name in ("groups",)}
+
+
 def side_lib_names() -> list:
     return list(SIDE_LIBS)
+
+
+def every_side_lib_names() -> list:
+    """side_lib_names() and the libraries of MORE_SIDE_LIBS, in build order"""
+    return list(SIDE_LIBS) + list(MORE_SIDE_LIBS)
+
+
+def _side_lib(name) -> SideLib:
+    return SIDE_LIBS[name] if name in SIDE_LIBS else MORE_SIDE_LIBS[name]
 
 
 def _parse_usage(text: str) -> dict:
@@ -83,13 +101,13 @@ def _includes(path, seen=None) -> set:
 
 
 def _side_deps(name) -> list:
-    return sorted(_includes(os.path.join(CSRC, SIDE_LIBS[name].source))) + [os.path.abspath(__file__)]
+    return sorted(_includes(os.path.join(CSRC, _side_lib(name).source))) + [os.path.abspath(__file__)]
 
 
 def _product_deps() -> list:
     """every file of csrc/ that is not a side library's source or a header only side libraries include"""
     ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
-    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in SIDE_LIBS.values())) - ours
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(_side_lib, every_side_lib_names()))) - ours
     return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
 
@@ -133,8 +151,9 @@ def _link(lib, objs, usage, usage_path, verbose) -> str:
 
 
 def build_side(name, force: bool = False, verbose: bool = True) -> str:
-    """SIDE_LIBS[name]: its one source -> its own library with the product FLAGS and the packed-fp32 fence, resource report -> .usage"""
-    sl = SIDE_LIBS[name]
+    """a side library (SIDE_LIBS or MORE_SIDE_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
+    resource report -> .usage"""
+    sl = _side_lib(name)
     if not force and not _stale(sl.lib, _side_deps(name)):
         return sl.lib
     bdir = os.path.dirname(sl.usage)
@@ -147,7 +166,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
     The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        for name in SIDE_LIBS:
+        for name in every_side_lib_names():
             build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):

@@ -3,6 +3,7 @@
 // pair of a gallery (few_shot.py:1115-1124, 2657-2687, 2970-2990) as one exact-fp32 MFMA GEMM with the soft-min DPs in its epilogue.
 // A library of its own: libclipfsar_hip.so keeps exactly the entry points of include/clipfsar_hip.h.
 #include "otam_tile.h"
+#include "topk_wave.h"
 #include "../../include/clipfsar_gallery.h"
 
 namespace {
@@ -71,55 +72,11 @@ __global__ __launch_bounds__(256) void otam_gallery_kernel(const float* __restri
     otam_tile<TT>(Xq, qn, P, DenseClasses{pn, dists_out}, logits, NQ, C, Trt, E, lbda, single_direct);
 }
 
-// ---- top-k per query: one wave per query.  Each lane keeps the best KMAX of its strided classes (a compare-exchange chain with
-// constant indices: registers only), then k rounds of a wave-wide arg-max over the lanes' heads.  Order: larger value first, the
-// lower class index on ties (a stable descending sort).  A NaN logit is never selected, and neither is one of -inf: -inf is the value
-// of an empty place, whose index is 0x7fffffff (no class).  The loop skips both; before it did, a -inf class was kept with its index
-// when its lane already held a class and lost it to 0x7fffffff when it was the lane's first.
-constexpr int KMAX = 16;
-__device__ __forceinline__ bool topk_better(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
+// ---- top-k per query: one wave per query, topk_wave (topk_wave.h)
 __global__ __launch_bounds__(64) void topk_kernel(const float* __restrict__ logits, float* __restrict__ values,
                                                   int32_t* __restrict__ index, int C, int k) {
-    const int q = blockIdx.x, lane = threadIdx.x;
-    float v[KMAX];
-    int ix[KMAX];
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) { v[j] = -__builtin_inff(); ix[j] = 0x7fffffff; }
-    const float* row = logits + (size_t)q * C;
-    for (int c = lane; c < C; c += 64) {
-        float x = row[c];
-        int xi = c;
-        if (!(x > -__builtin_inff())) continue;            // NaN or -inf: not selectable
-#pragma unroll
-        for (int j = 0; j < KMAX; ++j) {
-            if (topk_better(x, xi, v[j], ix[j])) {
-                const float tv = v[j];
-                const int ti = ix[j];
-                v[j] = x; ix[j] = xi; x = tv; xi = ti;
-            }
-        }
-    }
-    for (int r = 0; r < k; ++r) {
-        float bv = v[0];
-        int bi = ix[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (topk_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) {
-            values[(size_t)q * k + r] = bv;
-            index[(size_t)q * k + r] = bi;
-        }
-        if (ix[0] == bi) {                                 // the winner's lane pops its head
-#pragma unroll
-            for (int j = 0; j < KMAX - 1; ++j) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
-            v[KMAX - 1] = -__builtin_inff();
-            ix[KMAX - 1] = 0x7fffffff;
-        }
-    }
+    const size_t q = blockIdx.x;
+    topk_wave(logits + q * C, C, k, values + q * k, index + q * k, threadIdx.x);
 }
 
 }  // namespace
@@ -171,7 +128,7 @@ extern "C" int cfsg_otam_gallery(const float* Xq, const float* qn, const float* 
 
 extern "C" int cfsg_topk(const float* logits, float* values, int32_t* index, int NQ, int C, int k, cfsg_stream_t stream) {
     SIDE_REQUIRE(logits && values && index, "cfsg_topk: null pointer");
-    SIDE_REQUIRE(NQ > 0 && C > 0 && C <= 65535 && k >= 1 && k <= KMAX && k <= C,
+    SIDE_REQUIRE(NQ > 0 && C > 0 && C <= 65535 && k >= 1 && k <= TOPK_MAX && k <= C,
                  "cfsg_topk: bad shape (NQ=%d C=%d k=%d; 1 <= k <= 16, k <= C <= 65535)", NQ, C, k);
     hipLaunchKernelGGL(topk_kernel, dim3((unsigned)NQ), dim3(64), 0, static_cast<hipStream_t>(stream), logits, values, index, C, k);
     return check_launch("cfsg_topk");

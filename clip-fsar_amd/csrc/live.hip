@@ -14,16 +14,12 @@ struct StoreSlots {
     const int32_t* __restrict__ cols;
     int cap;
     static constexpr bool POISONS = true;              // a bad slot: NaN norms poison its column
-    // store row of tile row r, or -1: r is past the tile's classes, or its slot is outside [0, cap) (never dereferenced)
-    __device__ __forceinline__ long long store_row(int r, int c0, int b_rows, int T) const {
-        if (r >= b_rows) return -1;
-        const int j = r / T, slot = cols[c0 + j];
-        return (unsigned)slot < (unsigned)cap ? (long long)slot * T + (r - j * T) : -1;
+    // store row of tile row r, or -1: r is past the tile's classes, or its slot is outside [0, cap) (store_slot_row, otam_tile.h)
+    __device__ __forceinline__ LookedUpRow row(int r, int c0, int b_rows, int T) const {
+        return LookedUpRow{store_slot_row(cols, cap, r, c0, b_rows, T)};
     }
-    __device__ __forceinline__ LookedUpRow row(int r, int c0, int b_rows, int T) const { return LookedUpRow{store_row(r, c0, b_rows, T)}; }
     __device__ __forceinline__ float norm(int r, int c0, int b_rows, int T) const {
-        const long long row = store_row(r, c0, b_rows, T);
-        return row >= 0 ? pn[row] : (r < b_rows ? __builtin_nanf("") : 1.f);
+        return store_slot_norm(pn, cols, cap, r, c0, b_rows, T);
     }
     __device__ __forceinline__ float* dists() const { return nullptr; }
 };

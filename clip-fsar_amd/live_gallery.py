@@ -11,6 +11,8 @@ in place, and between growths (1.5 x when full) the store's address does not mov
     g.remove_classes([3, 7])                     # the other columns close up in their order; layout_version rises
     logits = g.classify(queries, classes=[9, 2]) # [NQ, 2], columns in the order given; None: every class, in registration order
     values, index = g.topk(queries, k=5, classes=None)
+    r = g.classify_grouped(queries, counts=[3, 2], classes=[[9, 2], None])      # 3 clips against [9, 2], the next 2 against every class:
+    r.group(0), r.group(1), r.logits             # [3, 2] and [2, C] views of the flat logits; one scoring launch (libclipfsar_groups.so)
     g.shots(9); g.state_dict()                   # SupportGallery's keys (dense, column order) + "sums" and "counts"
 
 A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
@@ -25,6 +27,7 @@ import heapq
 import torch
 
 from . import gallery_hip as ghip
+from . import groups_hip as grhip
 from . import live_hip as lhip
 from .gallery import LAMBDA, _flag, _GalleryBase
 
@@ -132,6 +135,53 @@ def plan_columns(book, classes=None, name="LiveGallery"):
     return [book.slot_of[c] for c in classes]
 
 
+GroupPlan = collections.namedtuple("GroupPlan", "rows slots n_out")      # rows: groups_hip's table; slots: the lists, one after the other
+
+
+def plan_groups(book, counts, classes, T, name="LiveGallery"):
+    """counts[i] consecutive queries against classes[i] (plan_columns' rules per group; None: every class in column order) -> GroupPlan:
+    the descriptor table of the grouped kernels for frames of T, the concatenated slot lists and the number of logits"""
+    counts, classes = list(counts), list(classes)
+    if len(counts) != len(classes) or not counts:
+        raise ValueError("%s: grouped scoring needs groups and one count for each, got %d counts and %d class lists" % (
+            name, len(counts), len(classes)))
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 0 for n in counts):
+        raise ValueError("%s: a group's count must be an integer >= 0, got %r" % (name, counts))
+    lists = [plan_columns(book, c, "%s: group %d" % (name, i)) for i, c in enumerate(classes)]
+    for i, slots in enumerate(lists):
+        if not slots:                                         # None on a gallery without classes
+            raise ValueError("%s: group %d: classes= needs at least one class" % (name, i))
+    rows, (_, _, _, n_out) = grhip.table_rows(counts, [len(l) for l in lists], T)
+    return GroupPlan(rows, [s for l in lists for s in l], n_out)
+
+
+def chunk_groups(rows, q0, q1, T):
+    """The part of a table that the queries q0 .. q1-1 (q0 < q1) reach, as a table of its own: (rows, (first, end) of its lists in the slot
+    list, the first logit it owns).  The groups from the first to the last one with a query in the range, those between without queries
+    included: their lists and their logits are contiguous in the whole call's, so the chunk's launch works on slices."""
+    hit = [g for g, r in enumerate(rows) if r[grhip.NQ] and r[grhip.Q0] < q1 and r[grhip.Q0] + r[grhip.NQ] > q0]
+    part = rows[hit[0]:hit[-1] + 1]
+    counts = [max(0, min(q1, r[grhip.Q0] + r[grhip.NQ]) - max(q0, r[grhip.Q0])) for r in part]
+    first, last = part[0], part[-1]
+    sub, _ = grhip.table_rows(counts, [r[grhip.NC] for r in part], T)
+    return sub, (first[grhip.C0], last[grhip.C0] + last[grhip.NC]), first[grhip.OUT0] + (q0 - first[grhip.Q0]) * first[grhip.NC]
+
+
+class GroupedLogits:
+    """What grouped scoring returns: `logits`, flat, group i owning [offsets[i], offsets[i + 1]) as a row-major [counts[i], widths[i]]
+    block -- group(i) is that view."""
+    __slots__ = ("logits", "offsets", "widths", "counts")
+
+    def __init__(self, logits, offsets, widths, counts):
+        self.logits, self.offsets, self.widths, self.counts = logits, offsets, widths, counts
+
+    def __len__(self):
+        return len(self.counts)
+
+    def group(self, i):
+        return self.logits[self.offsets[i]:self.offsets[i + 1]].view(self.counts[i], self.widths[i])
+
+
 # ---------------------------------------------------------------------------------------------------------------- the gallery
 class LiveGallery(_GalleryBase):
     def __init__(self, head, device="cuda", capacity=64):
@@ -149,7 +199,7 @@ class LiveGallery(_GalleryBase):
         self._capacity = capacity
         self._store = None                                 # allocated by the first call that needs the device
         self._retired = []                                 # (outgrown store, the event behind the work queued on it)
-        self._tables = None
+        self._tables = self._group_tables = None
         self._book = self._active = None
         self.clear()
 
@@ -166,6 +216,7 @@ class LiveGallery(_GalleryBase):
         self._ids = book.order                             # _GalleryBase: len(), class_ids, "no classes registered"
         self._cols = None                                  # device column list of all classes, made on demand
         self._subset = (None, None)                        # the last classes= list and its device columns
+        self._group_cols = (None, None)                    # the last grouped call's slot lists and their device copy
 
     @property
     def layout_version(self):
@@ -342,6 +393,85 @@ class LiveGallery(_GalleryBase):
         Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
         ghip.row_norms(Xq, ws["qn"])
         lhip.otam_indexed(Xq, ws["qn"], st["P"], st["pn"], self._active, out, LAMBDA, self.single_direct)
+
+    # ------------------------------------------------------------------ grouped classification
+    def _upload_groups(self, rows):
+        if self._group_tables is None or self._group_tables.max_rows < len(rows):
+            self._group_tables = grhip.table_uploader(self.dev, max(TABLE_ROWS, len(rows)))
+        return self._group_tables.upload(rows)
+
+    def _plan_groups(self, counts, classes):
+        """plan_groups, with what only the gallery knows: whether there are classes, and the library's group limit"""
+        counts = [c.item() if isinstance(c, torch.Tensor) else c for c in (counts.reshape(-1).cpu() if isinstance(counts, torch.Tensor)
+                                                                           else counts)]
+        if not self._ids:
+            raise RuntimeError("%s: no classes registered" % self._name)
+        plan = plan_groups(self._book, counts, classes, self.T, self._name)
+        if len(plan.rows) > grhip.MAX_GROUPS:
+            raise ValueError("%s: %d groups, the grouped library scores at most %d per call" % (self._name, len(plan.rows),
+                                                                                              grhip.MAX_GROUPS))
+        return plan
+
+    def _classify_groups(self, src, tower, counts, classes):
+        eng = self._fresh_engine()
+        plan = self._plan_groups(counts, classes)             # every error before the device is touched
+        src = self._check_videos(src, "queries") if tower else self._check_feats(src)
+        N = sum(r[grhip.NQ] for r in plan.rows)
+        if N != src.shape[0] or N < 1:
+            raise ValueError("%s: the groups' counts add up to %d, the call holds %d clips (at least 1 is needed)" % (
+                self._name, N, src.shape[0]))
+        key = tuple(plan.slots)
+        if self._group_cols[0] != key:
+            self._group_cols = (key, torch.tensor(plan.slots, device=self.dev, dtype=torch.int32))
+        cols, st, T = self._group_cols[1], self._store, self.T
+        out = torch.empty(plan.n_out, device=self.dev, dtype=torch.float32)
+        chunk = max(1, eng.max_frames // T)                   # _GalleryBase._classify's chunks: a chunk may start and end inside groups
+        for q0 in range(0, N, chunk):
+            q1 = min(N, q0 + chunk)
+            n = q1 - q0
+            ws = self._query_ws(n)
+            feats = src[q0:q1]
+            if tower:
+                feats = ws["feats"]
+                self._features(eng, src[q0:q1], feats)
+            rows, (c_lo, c_hi), out_lo = chunk_groups(plan.rows, q0, q1, T)
+            n_out = sum(r[grhip.NQ] * r[grhip.NC] for r in rows)
+            Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
+            ghip.row_norms(Xq, ws["qn"])
+            grhip.otam_grouped(Xq, ws["qn"], st["P"], st["pn"], cols[c_lo:c_hi], out[out_lo:out_lo + n_out], self._upload_groups(rows),
+                               n_out, LAMBDA, self.single_direct)
+        offsets = [r[grhip.OUT0] for r in plan.rows] + [plan.n_out]
+        return GroupedLogits(out, offsets, [r[grhip.NC] for r in plan.rows], [r[grhip.NQ] for r in plan.rows]), plan
+
+    def classify_grouped(self, queries, counts, classes):
+        """queries [NQ, T, 3, H, W] fp32 (device): counts[i] consecutive clips form group i and are scored against classes[i] (registered
+        ids, any order, no repeats within a list; None: every class in registration order) -> GroupedLogits.  group(i) is what
+        classify(those clips, classes=classes[i]) gives; the tower and context2 run once over all clips and every chunk of clips is
+        scored by one launch, whatever the number of groups.  Lists may overlap and differ in length; a count may be 0."""
+        return self._classify_groups(queries, True, counts, classes)[0]
+
+    def classify_features_grouped(self, feats, counts, classes):
+        """feats [N, T, E] fp32 (device), the tower features of N clips -> what classify_grouped gives for those clips"""
+        return self._classify_groups(feats, False, counts, classes)[0]
+
+    def topk_grouped(self, queries, counts, classes, k=5):
+        """(values [NQ, k] fp32 descending, index [NQ, k] int32 into the query's own group's list -- into class_ids for a group of None);
+        ties go to the lower index.  k is at most the shortest list of a group with clips."""
+        plan = self._plan_groups(counts, classes)
+        widths = [r[grhip.NC] for r in plan.rows if r[grhip.NQ]]
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min([grhip.TOPK_MAX] + widths):
+            raise ValueError("%s.topk_grouped: k must be in [1, min(16, the shortest class list of a group with clips)], got %r" % (
+                self._name, k))
+        res, plan = self._classify_groups(queries, True, counts, classes)
+        return self.topk_of_groups(res.logits, plan.rows, k)
+
+    def topk_of_groups(self, logits, rows, k):
+        """top-k of flat grouped logits under the table `rows` (groups_hip.table_rows) -> (values, index), a row per query"""
+        N = sum(r[grhip.NQ] for r in rows)
+        values = torch.empty(N, k, device=self.dev, dtype=torch.float32)
+        index = torch.empty(N, k, device=self.dev, dtype=torch.int32)
+        grhip.topk_grouped(logits, self._upload_groups(rows), N, logits.shape[0], k, values, index)
+        return values, index
 
     # ------------------------------------------------------------------ state dict
     def state_dict(self):

@@ -10,6 +10,9 @@
     p.push_u8({a: ua, b: ub}); p.push_u8_packed([ua, ub], [a, b])     # decoded uint8 [n, H, W, 3] clips, each of its own H x W, on the host
                                                                       # or the device: clip_fsar_amd.ingest.FrameIngest, then push_packed
     values, index = p.topk(po, k=5)
+    c = p.open(classes=[9, 2])             # a session with columns of its own (a tenant's classes); needs a LiveGallery and smooth = 0
+    out = p.push({a: fa, c: fc})           # out[c].logits [nWc, 2], out[a].logits [nWa, C]: still one tower call sequence, and one grouped
+                                           # scoring launch per chunk of windows; the *_packed forms then return a GroupedPackedOutput
     p.reset(a); p.close(a); p.stats(a); p.stats()
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
@@ -31,12 +34,16 @@ import heapq
 import torch
 
 from . import gallery_hip as ghip
+from . import groups_hip as grhip
 from . import pool_hip as php
 from .gallery import _GalleryBase
 from .ingest import FrameIngest
 from .stream import StreamOutput, window_plan
 
 PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
+# Of a push in which a session has a class list of its own: logits is flat, session i owning [logit_offsets[i], logit_offsets[i + 1]) as
+# a row-major [offsets[i + 1] - offsets[i], widths[i]] block (windows ascending).
+GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions first_window offsets logits logit_offsets widths")
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
@@ -76,10 +83,11 @@ def plan_push(sessions, counts, T, stride, rate, max_push, smoothing=False):
 
 
 class _Session:
-    __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout")
+    __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout", "classes")
 
-    def __init__(self, slot):
+    def __init__(self, slot, classes=None):
         self.slot = slot
+        self.classes = classes                   # the session's own class list (open(classes=)), or None: every class; reset() keeps it
         self.clear()
 
     def clear(self):
@@ -124,15 +132,32 @@ class StreamPool:
         self._ingest = ingest                    # push_u8's transform; None: built from gallery.head.args by the first push_u8
 
     # ------------------------------------------------------------------ sessions
-    def open(self):
-        """a new session, its frames numbered from 0 -> its handle"""
+    def open(self, classes=None):
+        """a new session, its frames numbered from 0 -> its handle.  classes: registered class ids (any order, no repeats) -- the session
+        is scored against these alone, its logits' columns in the order given; None: every class, in registration order."""
+        if classes is not None:
+            classes = list(classes)
+            if not hasattr(self.gallery, "classify_features_grouped"):
+                raise ValueError("StreamPool: open(classes=) needs a gallery that scores groups (a LiveGallery), not a %s"
+                                 % type(self.gallery).__name__)
+            if self.alpha:
+                raise ValueError("StreamPool: open(classes=) on a pool with smooth > 0 is not supported -- smoothing with per-session "
+                                 "class lists is out of scope; build the pool with smooth = 0")
+            self._session_lists([self._next_handle], [classes])
         if not self._free:
             raise RuntimeError("StreamPool: all %d slots are in use -- close() a session or build the pool with a larger max_streams"
                                % self.max_streams)
         h = self._next_handle
         self._next_handle += 1
-        self._sessions[h] = _Session(heapq.heappop(self._free))
+        self._sessions[h] = _Session(heapq.heappop(self._free), classes)
         return h
+
+    def _session_lists(self, handles, lists):
+        """the sessions' class lists under the gallery's rules (registered, no repeats, not empty); an error names the session"""
+        from .live_gallery import plan_columns
+        for h, classes in zip(handles, lists):
+            if classes is not None:
+                plan_columns(self.gallery._book, classes, "StreamPool: session %d" % h)
 
     def _session(self, h):
         s = self._sessions.get(h) if isinstance(h, int) and not isinstance(h, bool) else None
@@ -193,6 +218,7 @@ class StreamPool:
         return recs, counts
 
     def _check_state(self, sessions, recs):
+        self._session_lists(sessions, [s.classes for s in recs])         # a class removed since open(): raised here, before any launch
         if self.alpha:
             C = len(self.gallery)
             fresh = self._state is None or self._state.shape[1] != C
@@ -241,10 +267,14 @@ class StreamPool:
 
     @staticmethod
     def _split(po):
-        """PackedOutput -> {session: StreamOutput}"""
+        """PackedOutput or GroupedPackedOutput -> {session: StreamOutput}"""
         out = {}
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
+            if isinstance(po, GroupedPackedOutput):
+                block = po.logits[po.logit_offsets[i]:po.logit_offsets[i + 1]]
+                out[h] = StreamOutput(po.first_window[i], block.view(w1 - w0, po.widths[i]), None)
+                continue
             out[h] = StreamOutput(po.first_window[i], po.logits[w0:w1], None if po.smoothed is None else po.smoothed[w0:w1])
         return out
 
@@ -288,17 +318,12 @@ class StreamPool:
             raise ValueError("StreamPool: a push takes a non-empty dict {session: uint8 [n, H, W, 3] frames}")
         return self._split(self.push_u8_packed(list(clips.values()), list(clips)))
 
-    def _run(self, eng, feats, handles, recs, counts):
-        g, T, C = self.gallery, self.T, len(self.gallery)
-        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push, smoothing=bool(self.alpha))
-        NW = sum(plan.n_windows)
-        logits = torch.empty(NW, C, device=self.dev, dtype=torch.float32)
-        smoothed = torch.empty_like(logits) if self.alpha else None
-        if self.alpha and NW and (self._state is None or self._state.shape[1] != C):
-            self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
-            self._state_gen += 1
+    def _gathered(self, eng, plan, feats):
+        """The device side of a push up to scoring: per round one table and one ring write, then per chunk of its windows one gather.
+        Yields (round, its table, its windows nW, chunk w0, w1, the chunk's windows X [w1 - w0, T, E]); a round without windows yields
+        nothing."""
+        T = self.T
         per = max(1, eng.max_frames // T)        # classify_features scores that many clips per chunk: gather no more at a time
-        g0 = 0
         for rnd in plan.rounds:
             if len(plan.rounds) == 1:
                 piece = feats
@@ -311,15 +336,62 @@ class StreamPool:
                 continue
             if self._X is None or self._X.shape[0] < min(nW, per):
                 self._X = torch.empty(min(nW, per), T, self.E, device=self.dev, dtype=torch.float32)
-            out = logits[g0:g0 + nW]
             for w0 in range(0, nW, per):
                 w1 = min(nW, w0 + per)
                 X = self._X[:w1 - w0]
                 php.window_sequences(self._ring, X, table, nW, w0, w1, T, self.stride, self.rate)
-                out[w0:w1].copy_(g.classify_features(X))
-            if self.alpha:
-                php.smooth_logits(out, self._state, smoothed[g0:g0 + nW], table, self.alpha)
-            g0 += nW
+                yield rnd, table, nW, w0, w1, X
+
+    def _run_grouped(self, eng, feats, handles, recs, counts):
+        """_run of a push in which a session has a class list: every chunk of windows is scored by one grouped launch, each session's
+        windows against its own list (None: every class) -> GroupedPackedOutput"""
+        g, T = self.gallery, self.T
+        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push)
+        lists = [s.classes for s in recs]
+        widths = [len(g) if c is None else len(c) for c in lists]
+        offsets, logit_offsets = [0], [0]
+        for nW, C in zip(plan.n_windows, widths):
+            offsets.append(offsets[-1] + nW)
+            logit_offsets.append(logit_offsets[-1] + nW * C)
+        logits = torch.empty(logit_offsets[-1], device=self.dev, dtype=torch.float32)
+        done = [0] * len(recs)                   # windows of each session scored so far: its block fills in window order
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+            # the chunk's windows session by session: row j of the round holds windows WIN_OFF .. WIN_OFF + NW - 1 of the round's list
+            part = [(i, max(0, min(w1, r[php.WIN_OFF] + r[php.NW]) - max(w0, r[php.WIN_OFF]))) for i, r in zip(rnd.members, rnd.rows)]
+            part = [(i, n) for i, n in part if n]
+            res = g.classify_features_grouped(X, [n for _, n in part], [lists[i] for i, _ in part])
+            if w1 - w0 == offsets[-1]:           # one chunk holds every window of the push: its flat logits are the push's
+                logits = res.logits
+                continue
+            for j, (i, n) in enumerate(part):
+                at = logit_offsets[i] + done[i] * widths[i]
+                logits[at:at + n * widths[i]].copy_(res.logits[res.offsets[j]:res.offsets[j + 1]])
+                done[i] += n
+        for s, n in zip(recs, counts):
+            s.t += n
+        self._totals["frames"] += sum(counts)
+        self._totals["windows"] += offsets[-1]
+        return GroupedPackedOutput(handles, plan.first_window, offsets, logits, logit_offsets, widths)
+
+    def _run(self, eng, feats, handles, recs, counts):
+        if any(s.classes is not None for s in recs):
+            return self._run_grouped(eng, feats, handles, recs, counts)
+        g, T, C = self.gallery, self.T, len(self.gallery)
+        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push, smoothing=bool(self.alpha))
+        NW = sum(plan.n_windows)
+        logits = torch.empty(NW, C, device=self.dev, dtype=torch.float32)
+        smoothed = torch.empty_like(logits) if self.alpha else None
+        if self.alpha and NW and (self._state is None or self._state.shape[1] != C):
+            self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
+            self._state_gen += 1
+        g0 = 0
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+            out = logits[g0:g0 + nW]
+            out[w0:w1].copy_(g.classify_features(X))
+            if w1 == nW:                         # the round's last chunk
+                if self.alpha:
+                    php.smooth_logits(out, self._state, smoothed[g0:g0 + nW], table, self.alpha)
+                g0 += nW
         if plan.order is not None and NW:        # several rounds: round-major -> session-major
             index = torch.tensor(plan.order, device=self.dev)
             logits = logits.index_select(0, index)
@@ -336,9 +408,24 @@ class StreamPool:
         return PackedOutput(handles, plan.first_window, offsets, logits, smoothed)
 
     # ------------------------------------------------------------------ top-k
+    def _topk_grouped(self, out, k, smoothed):
+        if smoothed:
+            raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")
+        n_windows = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])]
+        widths = [C for nW, C in zip(n_windows, out.widths) if nW]
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min([grhip.TOPK_MAX] + widths):
+            raise ValueError("StreamPool.topk: k must be in [1, min(16, the shortest class list of a session with windows)], got %r" % (k,))
+        if not out.offsets[-1]:
+            return (torch.empty(0, k, device=self.dev, dtype=torch.float32), torch.empty(0, k, device=self.dev, dtype=torch.int32))
+        rows, _ = grhip.table_rows(n_windows, out.widths, self.T)
+        return self.gallery.topk_of_groups(out.logits, rows, k)
+
     def topk(self, out, k=5, smoothed=False):
         """(values [nW, k] fp32 descending, class index [nW, k] int32 into gallery.class_ids) of every window of a PackedOutput or a
-        StreamOutput (of out.smoothed with smoothed=True); ties go to the lower index"""
+        StreamOutput (of out.smoothed with smoothed=True); ties go to the lower index.  Of a session with a class list of its own, and of
+        a GroupedPackedOutput, the index counts within that session's list, and k is at most the shortest list of a session with windows."""
+        if isinstance(out, GroupedPackedOutput):
+            return self._topk_grouped(out, k, smoothed)
         src = out.smoothed if smoothed else out.logits
         if src is None:
             raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")
