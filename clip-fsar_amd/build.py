@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -55,6 +55,14 @@ MORE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%
                   for name in ("groups",)}
 
 
+# Libraries of the image tower (the engine's forward loads them on first use), by the same move: the same SideLib tuple, recipe and call
+# sites in a third dict, because side_lib_names() and every_side_lib_names() are pinned by the checks of the libraries before them too.
+# "lastblock": the last block's class-token attention without its K | V projection, C ABI in include/clipfsar_lastblock.h.
+TOWER_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
+                            os.path.join(HERE, "build", name, "resource_usage.json"))
+              for name in ("lastblock",)}
+
+
 def side_lib_names() -> list:
     return list(SIDE_LIBS)
 
@@ -64,8 +72,20 @@ def every_side_lib_names() -> list:
     return list(SIDE_LIBS) + list(MORE_SIDE_LIBS)
 
 
+def tower_lib_names() -> list:
+    return list(TOWER_LIBS)
+
+
+def _all_lib_names() -> list:
+    """every library built beside the product library, in build order"""
+    return every_side_lib_names() + tower_lib_names()
+
+
 def _side_lib(name) -> SideLib:
-    return SIDE_LIBS[name] if name in SIDE_LIBS else MORE_SIDE_LIBS[name]
+    for libs in (SIDE_LIBS, MORE_SIDE_LIBS):
+        if name in libs:
+            return libs[name]
+    return TOWER_LIBS[name]
 
 
 def _parse_usage(text: str) -> dict:
@@ -107,7 +127,7 @@ def _side_deps(name) -> list:
 def _product_deps() -> list:
     """every file of csrc/ that is not a side library's source or a header only side libraries include"""
     ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
-    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(_side_lib, every_side_lib_names()))) - ours
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(_side_lib, _all_lib_names()))) - ours
     return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
 
@@ -151,7 +171,7 @@ def _link(lib, objs, usage, usage_path, verbose) -> str:
 
 
 def build_side(name, force: bool = False, verbose: bool = True) -> str:
-    """a side library (SIDE_LIBS or MORE_SIDE_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
+    """a side library (SIDE_LIBS, MORE_SIDE_LIBS or TOWER_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
     resource report -> .usage"""
     sl = _side_lib(name)
     if not force and not _stale(sl.lib, _side_deps(name)):
@@ -166,7 +186,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
     The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        for name in every_side_lib_names():
+        for name in _all_lib_names():
             build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):

@@ -59,7 +59,7 @@ class HipViT:
     # statistics fusion.  They are constructor arguments -- the product path reads four environment variables only (CFSAR_LN_FOLD,
     # CFSAR_FULL_LAST_BLOCK, CFSAR_FP16_SPLIT, CFSAR_FP16_MCORR).
     OPTIONS = {"fp16_wide": True, "fp16_lo": True, "fp16_rawmeans": True, "fused_umeans": True, "fused_omeans": True, "fuse_stats": True,
-               "fused_patch": True, "strict_front": True, "strict_o_pair": False}
+               "fused_patch": True, "strict_front": True, "strict_o_pair": False, "fold_last_kv": True}
 
     def __init__(self, arch: dict, sd: dict, prefix: str = "", precision: str = "bf16", device="cuda", stream_dtype=None, fp16_split=None, fp16_mcorr=None,
                  options=None):
@@ -248,6 +248,14 @@ class HipViT:
         # (K and V still come from all tokens): -6.3 % of the tower's FLOPs (ViT-B/16, 12 layers), same class-token arithmetic.
         # CFSAR_FULL_LAST_BLOCK=1 computes the whole block like the reference's PyTorch code does (taps always do).
         self.prune_last = os.environ.get("CFSAR_FULL_LAST_BLOCK", "0") != "1"
+        # Option fold_last_kv (bf16 mode, folded path): the pruned last block computes no K | V rows either.  Its one query per frame uses them
+        # through two linear functionals per head, and both apply to the raw stream: g = Wk'^T q / 8, softmax of (x_t . g - mu_t G) / sd_t,
+        # z = sum_t p_t (x_t - mu_t) / sd_t, o = Wv' z + d_v (include/clipfsar_lastblock.h; DESIGN.md "Last block").  Three launches of
+        # libclipfsar_lastblock.so (loaded on the first forward that needs it) replace the K | V GEMM over all tokens and cfsar_vit_attention_cls.
+        self.fold_last_kv = bool(opt["fold_last_kv"] and precision == "bf16" and self.fold and self.H <= 16)
+        if self.fold_last_kv:
+            blk = self.blocks[-1]
+            blk["wk_t"] = blk["wg_qkv"][D:2 * D].view(self.H, 64, D).transpose(1, 2).contiguous()    # [heads, D, 64]: layout only
         # LN statistics finalized inside the consuming GEMM (ViT-B / ViT-L widths; CFSAR_FUSE_STATS=0: the separate finalize launches)
         self.fuse_stats = bool(self.fold) and hip.lnfold_partials_ok(self.D, self.D // 64) and opt["fuse_stats"]
         self.fused_umeans = opt["fused_umeans"]      # c_fc emits the hidden's per-frame means (A/B switch)
@@ -331,6 +339,10 @@ class HipViT:
                 ws["xlo"] = torch.empty(M, D, device=dev, dtype=torch.float16)                # second word of the stream
                 ws["xlc"] = torch.empty(F_, D, device=dev, dtype=torch.float16)
                 ws["c32"] = torch.empty(F_, D, device=dev, dtype=torch.float32)
+            if self.fold_last_kv:                                                            # key fold, its column sums, class attend
+                ws["g"] = torch.empty(F_, self.H, D, device=dev, dtype=torch.float16)
+                ws["G"] = torch.empty(F_, self.H, device=dev, dtype=torch.float32)
+                ws["z"] = torch.empty(F_, self.H, D, device=dev, dtype=torch.float32)
             ws["xc"] = torch.empty(F_, D, device=dev, dtype=self.xd)
             ws["hc"] = torch.empty(F_, D, device=dev, dtype=cd)
             ws["oc"] = torch.empty(F_, D, device=dev, dtype=cd)
@@ -459,9 +471,11 @@ class HipViT:
                     xc, oc, uc, partc, rstatc = ws["xc"][:F_], ws["oc"][:F_], ws["uc"][:F_], ws["partc"][:F_], ws["rstatc"][:F_]
                     xlc = ws["xlc"][:F_] if xlo is not None else None
                     # ... and of q only the class-token rows: K | V for all M rows (N = 2 D: two thirds of the QKV GEMM), q for F rows
+                    # (option fold_last_kv: no K | V rows at all, the query is folded into the stream's rows below)
                     kv = qkv.view(-1)[:M * 2 * D].view(M, 2 * D)
-                    fold(x, b["wg_qkv"][D:], kv, b["cx_qkv" if raw else "c_qkv"][D:], b["d_qkv"][D:], part, rstat, from_part=in_part, sp="qkv" in split,
-                         corr=mc(b, "qkv", x, rstat, wrows=slice(D, 3 * D)), corr_raw=raw)
+                    if not self.fold_last_kv:
+                        fold(x, b["wg_qkv"][D:], kv, b["cx_qkv" if raw else "c_qkv"][D:], b["d_qkv"][D:], part, rstat, from_part=in_part,
+                             sp="qkv" in split, corr=mc(b, "qkv", x, rstat, wrows=slice(D, 3 * D)), corr_raw=raw)
                     class_rows(x, xc, D, es)                                          # class-token rows of the stream
                     if xlo is not None:
                         class_rows(xlo, xlc, D, 2)
@@ -474,7 +488,14 @@ class HipViT:
                         fold(xc, b["wgs_qkv"], qc, b["cs_qkv"], b["d_qkv"][:D], partc, rstatc, rows=F_, from_part=in_part, sp=True)
                     else:
                         fold(xc, b["wg_qkv"][:D], qc, b["c_qkv"][:D], b["d_qkv"][:D], partc, rstatc, rows=F_, from_part=in_part, sp="qkv" in split)
-                    hip.vit_attention_cls(None, oc, F_, N, D, self.H, q=qc, kv=kv)
+                    if self.fold_last_kv:
+                        from . import lastblock_hip as lb
+                        g_, G_, z_ = ws["g"][:F_], ws["G"][:F_], ws["z"][:F_]
+                        lb.key_fold(qc, b["wk_t"], g_, G_)
+                        lb.class_attend(x, g_, G_, z_, N, partial=part if in_part else None, rowstats=None if in_part else rstat)
+                        lb.value_fold(z_, b["wg_qkv"][2 * D:], b["d_qkv"][2 * D:], oc)
+                    else:
+                        hip.vit_attention_cls(None, oc, F_, N, D, self.H, q=qc, kv=kv)
                     resid(oc, b, "out", xc, xlc, partc, F_, cls=True)
                     if not fuse:
                         hip.ln_stats_finalize(partc, rstatc, F_, S, D)
