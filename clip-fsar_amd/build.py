@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS, LATER_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -63,6 +63,14 @@ TOWER_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so
               for name in ("lastblock",)}
 
 
+# Libraries added after those, by the same move once more: side_lib_names(), every_side_lib_names() and tower_lib_names() are each pinned by
+# the checks of the libraries before.  No name function is pinned to THIS dict, so a further library is one more name here.
+# "enroll": support sequences out of the stream pool's ring (StreamPool.enroll), C ABI in include/clipfsar_enroll.h.
+LATER_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
+                                 os.path.join(HERE, "build", name, "resource_usage.json"))
+                   for name in ("enroll",)}
+
+
 def side_lib_names() -> list:
     return list(SIDE_LIBS)
 
@@ -78,11 +86,11 @@ def tower_lib_names() -> list:
 
 def _all_lib_names() -> list:
     """every library built beside the product library, in build order"""
-    return every_side_lib_names() + tower_lib_names()
+    return every_side_lib_names() + tower_lib_names() + list(LATER_SIDE_LIBS)
 
 
 def _side_lib(name) -> SideLib:
-    for libs in (SIDE_LIBS, MORE_SIDE_LIBS):
+    for libs in (SIDE_LIBS, MORE_SIDE_LIBS, LATER_SIDE_LIBS):
         if name in libs:
             return libs[name]
     return TOWER_LIBS[name]
@@ -171,7 +179,7 @@ def _link(lib, objs, usage, usage_path, verbose) -> str:
 
 
 def build_side(name, force: bool = False, verbose: bool = True) -> str:
-    """a side library (SIDE_LIBS, MORE_SIDE_LIBS or TOWER_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
+    """a side library (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS or LATER_SIDE_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
     resource report -> .usage"""
     sl = _side_lib(name)
     if not force and not _stale(sl.lib, _side_deps(name)):

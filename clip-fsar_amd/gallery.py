@@ -171,7 +171,13 @@ class _GalleryBase:
     def _support_sequences(self, eng, videos, ids_of_video, new_ids, trows):
         """(X0 [Nv, T+1, E]: the support sequences grouped by class in the order of new_ids, video order inside a class; offs: the classes'
         runs in it, len(new_ids) + 1 prefix sums).  The tower runs in the caller's video order."""
-        Nv = videos.shape[0]
+        feats = torch.empty(videos.shape[0], self.T, self.E, device=self.dev, dtype=torch.float32)
+        self._features(eng, videos, feats)
+        return self._sequences_of_features(feats, ids_of_video, new_ids, trows)
+
+    def _sequences_of_features(self, feats, ids_of_video, new_ids, trows):
+        """_support_sequences after the tower: feats [Nv, T, E] in the caller's video order -> (X0, offs)"""
+        Nv = feats.shape[0]
         n = len(new_ids)
         local = {c: i for i, c in enumerate(new_ids)}
         order = sorted(range(Nv), key=lambda v: (local[ids_of_video[v]], v))     # videos grouped by class, video order inside a class
@@ -182,9 +188,7 @@ class _GalleryBase:
         for k in counts:
             offs.append(offs[-1] + k)
         T, E = self.T, self.E
-        # tower (in the caller's video order), then the class-grouped support sequences [Nv, T+1, E]
-        feats = torch.empty(Nv, T, E, device=self.dev, dtype=torch.float32)
-        self._features(eng, videos, feats)
+        # the class-grouped support sequences [Nv, T+1, E]
         feats = feats[torch.tensor(order, device=self.dev)].contiguous()
         cls_local = torch.tensor([local[ids_of_video[v]] for v in order], device=self.dev, dtype=torch.int32)
         X0 = torch.empty(Nv, T + 1, E, device=self.dev, dtype=torch.float32)

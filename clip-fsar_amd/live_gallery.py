@@ -8,6 +8,8 @@ in place, and between growths (1.5 x when full) the store's address does not mov
     g = LiveGallery(head, device, capacity=64)
     g.add_classes(videos, class_of_video)        # SupportGallery's arguments, errors, return value -- and its prototypes, bit for bit
     g.add_shots(videos, class_of_video)          # further examples of registered classes -> their shot counts
+    g.add_classes_features(feats, class_of_video); g.add_shots_features(feats, class_of_video)      # the same from tower features
+                                                 # [Nv, T, E]: the tower does not run (StreamPool.enroll feeds its ring's rows this way)
     g.remove_classes([3, 7])                     # the other columns close up in their order; layout_version rises
     logits = g.classify(queries, classes=[9, 2]) # [NQ, 2], columns in the order given; None: every class, in registration order
     values, index = g.topk(queries, k=5, classes=None)
@@ -270,12 +272,11 @@ class LiveGallery(_GalleryBase):
             self._tables = lhip.table_uploader(self.dev, TABLE_ROWS)
         return self._tables.upload([list(r) for r in rows])
 
-    def _update(self, eng, videos, ids_of_video, classes, trows, rows):
-        """videos of `classes` (first-appearance order; rows: their (slot, off, n, prior)) into the store: sums, prototypes, norms.
-        SupportGallery's launch sequence -- tower in the caller's order, context2 class by class -- with cfsl_accumulate in the place of
-        cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone."""
-        st, T, E, n = self._store, self.T, self.E, len(classes)
-        X0, offs = self._support_sequences(eng, videos, ids_of_video, classes, trows)
+    def _update_sequences(self, eng, X0, offs, rows):
+        """Support sequences X0 [Nv, T+1, E], grouped by class (class i = sequences offs[i] .. offs[i+1]-1; rows: the classes' (slot, off,
+        n, prior)) into the store: sums, prototypes, norms.  SupportGallery's launch sequence after the support sequences -- context2 class
+        by class -- with cfsl_accumulate in the place of cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone."""
+        st, T, E, n = self._store, self.T, self.E, len(rows)
         Y = None if self.merge_before else self._context2_by_class(eng, X0, offs)       # (:2955-2956)
         for c0 in range(0, n, TABLE_ROWS):
             c1 = min(n, c0 + TABLE_ROWS)
@@ -293,24 +294,70 @@ class LiveGallery(_GalleryBase):
             lhip.slot_norms(st["P"], st["pn"], table)
 
     # ------------------------------------------------------------------ registration, shots, removal
+    # Each has a pixel form and a feature form, which differ in how the support sequences come about: `sequences(ids_of_video, classes,
+    # trows) -> (X0, offs)` is _support_sequences behind the tower or _sequences_of_features without it.  What a call decides before the
+    # device is touched (plan_classes, plan_shots) and what it does with ready sequences (_register_sequences, _shots_sequences) are
+    # apart, so that StreamPool.enroll_windows, whose sequences come out of its ring, plans a whole call first and then uses the latter.
+    def _plan_classes(self, eng, ids_of_video, new_ids, text, book=None):
+        """-> (text rows of the new classes, their shot counts, AddPlan on `book`, default the gallery's); raises what add_classes raises
+        about the classes"""
+        trows = self._text_rows(eng, new_ids, text)
+        counts = [sum(1 for v in ids_of_video if v == c) for c in new_ids]
+        return trows, counts, plan_add(self._book if book is None else book, new_ids, counts, self._name)
+
+    def _register_sequences(self, eng, trows, counts, plan, sequences):
+        """the device work of a registration planned by _plan_classes; sequences(trows) -> (X0, offs).  -> the new column indices"""
+        st = self._ensure_store(plan.book.cap)
+        offs = [0]
+        for k in counts:
+            offs.append(offs[-1] + k)
+        X0, seq_offs = sequences(trows)
+        assert seq_offs == offs
+        self._update_sequences(eng, X0, offs, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)])
+        st["text"].index_copy_(0, torch.tensor(plan.slots, device=self.dev), trows)
+        C0 = len(self._book.order)
+        self._install(plan.book)
+        return list(range(C0, C0 + len(plan.slots)))
+
+    def _shots_sequences(self, eng, plan, sequences):
+        """the device work of further shots planned by plan_shots; sequences(trows) -> (X0, offs).  -> the classes' shot counts"""
+        st = self._store
+        trows = st["text"].index_select(0, torch.tensor([r[0] for r in plan.rows], device=self.dev))
+        X0, offs = sequences(trows)
+        self._update_sequences(eng, X0, offs, plan.rows)
+        self._book = plan.book                              # the columns did not change: _ids and the device lists stay
+        return [plan.book.shots[c] for c in plan.classes]
+
+    def _add_classes(self, eng, src, class_of_video, text, sequences_of):
+        ids_of_video, new_ids = self._video_classes(src, class_of_video, text)
+        trows, counts, plan = self._plan_classes(eng, ids_of_video, new_ids, text)
+        return self._register_sequences(eng, trows, counts, plan, lambda trows: sequences_of(src, ids_of_video, new_ids, trows))
+
+    def _shot_ids(self, class_of_video):
+        ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (
+            class_of_video.reshape(-1).cpu() if isinstance(class_of_video, torch.Tensor) else class_of_video)]
+        return [int(c) if isinstance(c, float) and c == int(c) else c for c in ids]
+
+    def _add_shots(self, eng, src, class_of_video, sequences_of):
+        ids = self._shot_ids(class_of_video)
+        if len(ids) != src.shape[0]:
+            raise ValueError("%s: %d videos but %d class ids" % (self._name, src.shape[0], len(ids)))
+        plan = plan_shots(self._book, ids, self._name)
+        return self._shots_sequences(eng, plan, lambda trows: sequences_of(src, ids, plan.classes, trows))
+
     def add_classes(self, videos, class_of_video, text=None):
         """SupportGallery.add_classes: the same arguments, errors, return value (the new classes' column indices) and prototypes; nothing but
         the new classes is written."""
         eng = self._fresh_engine()
         videos = self._check_videos(videos, "videos")
-        ids_of_video, new_ids = self._video_classes(videos, class_of_video, text)
-        trows = self._text_rows(eng, new_ids, text)
-        counts = [sum(1 for v in ids_of_video if v == c) for c in new_ids]
-        plan = plan_add(self._book, new_ids, counts, self._name)
-        st = self._ensure_store(plan.book.cap)
-        offs = [0]
-        for k in counts:
-            offs.append(offs[-1] + k)
-        self._update(eng, videos, ids_of_video, new_ids, trows, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)])
-        st["text"].index_copy_(0, torch.tensor(plan.slots, device=self.dev), trows)
-        C0 = len(self._book.order)
-        self._install(plan.book)
-        return list(range(C0, C0 + len(new_ids)))
+        return self._add_classes(eng, videos, class_of_video, text, lambda *a: self._support_sequences(eng, *a))
+
+    def add_classes_features(self, feats, class_of_video, text=None):
+        """add_classes of clips whose tower features feats [Nv, T, E] fp32 (device) exist already (a cache, a stream pool's ring): the same
+        arguments otherwise, errors, return value and prototypes, bit for bit; the tower does not run."""
+        eng = self._fresh_engine()
+        feats = self._check_feats(feats)
+        return self._add_classes(eng, feats, class_of_video, text, self._sequences_of_features)
 
     def add_shots(self, videos, class_of_video):
         """Further videos [Nv, T, 3, H, W] of registered classes (class_of_video [Nv]) join their classes after the existing shots: the
@@ -318,17 +365,13 @@ class LiveGallery(_GalleryBase):
         order."""
         eng = self._fresh_engine()
         videos = self._check_videos(videos, "videos")
-        ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (
-            class_of_video.reshape(-1).cpu() if isinstance(class_of_video, torch.Tensor) else class_of_video)]
-        ids = [int(c) if isinstance(c, float) and c == int(c) else c for c in ids]
-        if len(ids) != videos.shape[0]:
-            raise ValueError("%s: %d videos but %d class ids" % (self._name, videos.shape[0], len(ids)))
-        plan = plan_shots(self._book, ids, self._name)
-        st = self._store
-        trows = st["text"].index_select(0, torch.tensor([r[0] for r in plan.rows], device=self.dev))
-        self._update(eng, videos, ids, plan.classes, trows, plan.rows)
-        self._book = plan.book                              # the columns did not change: _ids and the device lists stay
-        return [plan.book.shots[c] for c in plan.classes]
+        return self._add_shots(eng, videos, class_of_video, lambda *a: self._support_sequences(eng, *a))
+
+    def add_shots_features(self, feats, class_of_video):
+        """add_shots of clips whose tower features feats [Nv, T, E] fp32 (device) exist already; the tower does not run."""
+        eng = self._fresh_engine()
+        feats = self._check_feats(feats)
+        return self._add_shots(eng, feats, class_of_video, self._sequences_of_features)
 
     def remove_classes(self, ids):
         """Drop registered classes: their slots become free (the lowest free slot is the next one taken), the remaining columns close up

@@ -13,6 +13,10 @@
     c = p.open(classes=[9, 2])             # a session with columns of its own (a tenant's classes); needs a LiveGallery and smooth = 0
     out = p.push({a: fa, c: fc})           # out[c].logits [nWc, 2], out[a].logits [nWa, C]: still one tower call sequence, and one grouped
                                            # scoring launch per chunk of windows; the *_packed forms then return a GroupedPackedOutput
+    p.enroll(a, class_id=7)                # the session's newest complete window becomes a shot of class 7 (a new class, or a further
+                                           # shot of a registered one) out of the ring's tower rows: the tower does not run.  Needs a LiveGallery
+    p.enrolable(a)                         # range of the window numbers still in the ring; p.enroll(a, 7, window=w, join=True)
+    p.enroll_windows([(a, None, 7), (b, 3, 7), (b, 4, "kite")], text={"kite": "flying a kite"})     # -> {7: 2, "kite": 1}
     p.reset(a); p.close(a); p.stats(a); p.stats()
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
@@ -25,6 +29,11 @@ A push is described to the device by one descriptor table with a row per session
 write per round, one gather plus one classify_features per chunk of windows, whatever the number of sessions.  A session's push beyond
 max_push frames is split into rounds (round r takes up to max_push of what each session has left).  Sessions absent from a push are
 untouched.  Smoothing state is per session: y_0 = x_0, y_k = fmaf(alpha, y_{k-1}, (1 - alpha) * x_k), the bits of WindowStream's.
+
+Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
+enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
+launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
+sessions changes: counters, ring, stats and smoothing state stay.
 """
 from __future__ import annotations
 
@@ -33,6 +42,7 @@ import heapq
 
 import torch
 
+from . import enroll_hip as enhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
@@ -82,6 +92,40 @@ def plan_push(sessions, counts, T, stride, rate, max_push, smoothing=False):
     return Plan(rounds, first_window, [len(w) for w in where], None if order == list(range(len(order))) else order)
 
 
+def enrolable_windows(t, T, stride, rate, cap):
+    """The windows of a session with t frames since open() / reset() that can still be enrolled, as a range.  The ring holds the frames
+    [max(0, t - cap), t); window w is the frames w * stride + j * rate, j = 0 .. T-1.  Enrolable: complete (w below the windows t frames
+    complete) and its first frame retained (w * stride >= t - cap).  With stride <= max_push the newest complete window always is."""
+    nW = window_plan(0, t, T, stride, rate)[1]
+    lo = -(-max(0, t - cap) // stride)
+    return range(lo, nW) if lo < nW else range(0)
+
+
+EnrollPlan = collections.namedtuple("EnrollPlan", "windows slots positions")
+
+
+def plan_enroll(sessions, requests, T, stride, rate, cap, names=None):
+    """The host plan of an enrolment.  sessions: (ring slot, frames pushed so far) per session; requests: (index into sessions, window
+    number or None: the session's newest complete window) -> EnrollPlan: per request the window number, the ring slot and the ring
+    position (w * stride) mod cap of the window's first frame.  Raises ValueError on a window that is not enrolable (names: what to call
+    each session in the message); changes nothing."""
+    windows, slots, positions = [], [], []
+    for i, w in requests:
+        slot, t = sessions[i]
+        ok = enrolable_windows(t, T, stride, rate, cap)
+        asked = w
+        if w is None:
+            w = window_plan(0, t, T, stride, rate)[1] - 1
+        if isinstance(w, bool) or not isinstance(w, int) or w not in ok:
+            w = "None (the newest complete one)" if asked is None else repr(w)
+            raise ValueError("%s: window %s is not enrolable -- the ring holds its windows %r (%d frames since open() / reset(), cap = %d)"
+                             % (names[i] if names else "session %d" % i, w, ok, t, cap))
+        windows.append(w)
+        slots.append(slot)
+        positions.append((w * stride) % cap)
+    return EnrollPlan(windows, slots, positions)
+
+
 class _Session:
     __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout", "classes")
 
@@ -121,6 +165,7 @@ class StreamPool:
         self._state = None                       # smoothing state [max_streams, C], indexed by slot
         self._state_gen = 0                      # bumped whenever _state is allocated anew (the class count changed)
         self._tables = php.TableUploader(self.dev, max_streams)
+        self._enroll_tables = None               # enrolment lists (enroll_hip's row layout), made by the first enroll
         self._sessions = {}                      # handle -> _Session
         self._free = list(range(max_streams))    # a heap: the lowest free slot is taken first
         self._next_handle = 0
@@ -406,6 +451,90 @@ class StreamPool:
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += NW
         return PackedOutput(handles, plan.first_window, offsets, logits, smoothed)
+
+    # ------------------------------------------------------------------ enrolment
+    def _enrolling_gallery(self):
+        g = self.gallery
+        if not hasattr(g, "add_shots_features"):
+            raise ValueError("StreamPool: enrolment needs a gallery that registers from features (a LiveGallery), not a %s"
+                             % type(g).__name__)
+        return g
+
+    def enrolable(self, h):
+        """range of the session's window numbers that enroll() accepts: complete, and their first frame still in the ring"""
+        self._enrolling_gallery()
+        return enrolable_windows(self._session(h).t, self.T, self.stride, self.rate, self.cap)
+
+    def _ring_sequences(self, trows, slots, positions, classes):
+        """one launch: the support sequences X0 [n, T+1, E] of the ring windows (slot, position), each closed by trows[classes[i]]"""
+        n = len(slots)
+        if self._enroll_tables is None or self._enroll_tables.max_rows < n:
+            self._enroll_tables = enhip.table_uploader(self.dev, max(1024, n))
+        X0 = torch.empty(n, self.T + 1, self.E, device=self.dev, dtype=torch.float32)
+        enhip.ring_sequences(self._ring, trows, self._enroll_tables.upload(enhip.table_rows(slots, positions, classes)), X0, self.rate)
+        return X0
+
+    def enroll_windows(self, items, text=None):
+        """items: [(session, window number or None: the session's newest complete window, class id), ...] -> {class id: its shot count}.
+        Every window becomes a shot of its class: of a registered class a further one (LiveGallery.add_shots' rules), of an unknown id
+        the first of a new class (add_classes' rules; its text from TEST.CLASS_NAME or from `text`).  Several windows of one class are its
+        shots in the order given.  The windows' tower rows are read out of the ring -- one launch for the new classes, one for the further
+        shots -- and the tower does not run.  Every error is raised before any launch and leaves the gallery as it was."""
+        from .live_gallery import plan_shots
+        g = self._enrolling_gallery()
+        eng = g._fresh_engine()
+        items = list(items) if isinstance(items, (list, tuple)) else None
+        if not items or any(not isinstance(it, (list, tuple)) or len(it) != 3 for it in items):
+            raise ValueError("StreamPool: enroll_windows takes a non-empty list of (session, window or None, class id)")
+        if text is not None and not isinstance(text, dict):
+            raise TypeError("StreamPool: `text` must map class id -> class name or [E] text row")
+        for h, _, _ in items:
+            self._session(h)
+        handles = list(dict.fromkeys(h for h, _, _ in items))
+        at = {h: i for i, h in enumerate(handles)}
+        plan = plan_enroll([(self._sessions[h].slot, self._sessions[h].t) for h in handles], [(at[h], w) for h, w, _ in items], self.T,
+                           self.stride, self.rate, self.cap, names=["StreamPool: session %d" % h for h in handles])
+        ids = g._shot_ids([c for _, _, c in items])
+        book = g._book
+        known = [i for i, c in enumerate(ids) if c in book.slot_of]
+        new = [i for i, c in enumerate(ids) if c not in book.slot_of]
+        shot_plan = add = None
+        if known:
+            shot_plan = plan_shots(book, [ids[i] for i in known], g._name)
+            book = shot_plan.book
+        if new:
+            new_ids = list(dict.fromkeys(ids[i] for i in new))
+            add = g._plan_classes(eng, [ids[i] for i in new], new_ids, text, book)
+        # ---- the device work: nothing below raises on the call's arguments
+        def sequences(members, classes):
+            """trows -> (X0, offs): the windows of the items `members` grouped by class in the order of `classes`, the caller's order
+            inside a class, each closed by its class's row of trows; one launch"""
+            local = {c: j for j, c in enumerate(classes)}
+            order = sorted(members, key=lambda i: (local[ids[i]], i))
+            offs = [0]
+            for c in classes:
+                offs.append(offs[-1] + sum(1 for i in members if ids[i] == c))
+            return lambda trows: (self._ring_sequences(trows, [plan.slots[i] for i in order], [plan.positions[i] for i in order],
+                                                       [local[ids[i]] for i in order]), offs)
+
+        result = {}
+        if known:
+            result.update(zip(shot_plan.classes, g._shots_sequences(eng, shot_plan, sequences(known, shot_plan.classes))))
+        if new:
+            trows, counts, add_plan = add
+            g._register_sequences(eng, trows, counts, add_plan, sequences(new, new_ids))
+            result.update(zip(new_ids, counts))
+        return {c: result[c] for c in dict.fromkeys(ids)}
+
+    def enroll(self, h, class_id, window=None, text=None, join=False):
+        """enroll_windows([(h, window, class_id)], text) -> the class's shot count.  join=True: a session opened with classes=[...] gets
+        the class appended to its list when it is not there (a session without a list sees every class anyway)."""
+        shots = self.enroll_windows([(h, window, class_id)], text)
+        cid = next(iter(shots))
+        s = self._sessions[h]
+        if join and s.classes is not None and cid not in s.classes:
+            s.classes = s.classes + [cid]
+        return shots[cid]
 
     # ------------------------------------------------------------------ top-k
     def _topk_grouped(self, out, k, smoothed):
