@@ -219,9 +219,9 @@ __global__ __launch_bounds__(256) void text_match_kernel(const float* __restrict
                                                          int Q, int T, int E, int way, int n_test) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* img = reinterpret_cast<float*>(smem);           // [E]
-    float* txt = img + E;                                  // [E]
     __shared__ int rank[MAX_S];
     __shared__ float red[4];
+    __shared__ float dotp[4];                              // per-wave dot partials: never in the dynamic block, which holds E floats and E may be 1
     __shared__ float logit[64];
     const int bq = blockIdx.x, b = bq / Q, q = bq - b * Q;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -259,11 +259,11 @@ __global__ __launch_bounds__(256) void text_match_kernel(const float* __restrict
         tt = wave_sum(tt);
         dot = wave_sum(dot);
         __syncthreads();
-        if (lane == 0) { red[wave] = tt; txt[wave] = dot; }
+        if (lane == 0) { red[wave] = tt; dotp[wave] = dot; }
         __syncthreads();
         if (tid == 0) {
             const float tn = sqrtf(red[0] + red[1] + red[2] + red[3]);
-            const float d = txt[0] + txt[1] + txt[2] + txt[3];
+            const float d = dotp[0] + dotp[1] + dotp[2] + dotp[3];
             logit[c] = scale[0] * (d / inorm / tn);
         }
     }
@@ -465,7 +465,7 @@ extern "C" int cfsar_text_match_probs(const float* feats, const float* text_test
                   "cfsar_text_match_probs: null pointer");
     CFSAR_REQUIRE(B > 0 && S > 0 && S <= MAX_S && Q > 0 && T > 0 && E > 0 && way > 0 && way <= 64 && n_test > 0,
                   "cfsar_text_match_probs: bad shape");
-    hipLaunchKernelGGL(text_match_kernel, dim3((unsigned)(B * Q)), dim3(256), 2 * E * sizeof(float),
+    hipLaunchKernelGGL(text_match_kernel, dim3((unsigned)(B * Q)), dim3(256), E * sizeof(float),
                        static_cast<hipStream_t>(stream), feats, text_test, support_labels, real_support_labels, scale, probs, S,
                        Q, T, E, way, n_test);
     return cfsar_check_launch("cfsar_text_match_probs");
@@ -473,7 +473,7 @@ extern "C" int cfsar_text_match_probs(const float* feats, const float* text_test
 
 namespace {
 // A17: per-episode top-1 accuracy.  One thread per episode: the first maximum of each query's `way` logits (torch.argmax / topk order) against
-// the query's label.
+// the query's label.  A NaN is the maximum, as it is for torch.argmax and torch.topk: the first NaN of a row wins and nothing replaces it.
 __global__ __launch_bounds__(64) void episode_top1_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
                                                           float* __restrict__ acc, int episodes, int Q, int way) {
     const int e = blockIdx.x * 64 + threadIdx.x;
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(64) void episode_top1_kernel(const float* __restric
         int best = 0;
         float bv = l[0];
         for (int c = 1; c < way; ++c)
-            if (l[c] > bv) { bv = l[c]; best = c; }
+            if (bv == bv && (l[c] > bv || l[c] != l[c])) { bv = l[c]; best = c; }
         hit += (best == (int)labels[(size_t)e * Q + q]);
     }
     acc[e] = (float)hit / (float)Q;

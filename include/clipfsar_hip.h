@@ -232,6 +232,7 @@ int cfsar_cos_otam_logits(const float* Xq, const float* protos, float* logits, f
 
 /* ---- A17 per-episode top-1 accuracy (utils/metrics.py:100-138 topks_correct with k = 1, per episode as runs/test_net_few_shot.py:120-147
  * uses it): acc[e] = fraction of episode e's Q queries whose first-maximum class equals target_labels[e, q] (class index as float).
+ * A NaN logit is the maximum, the first one of a row as for torch.argmax / torch.topk (the tail writes NaN rows for invalid labels).
  * logits [episodes, Q, way] f32, target_labels [episodes, Q] f32, acc [episodes] f32. */
 int cfsar_episode_top1(const float* logits, const float* target_labels, float* acc, int episodes, int Q, int way, cfsar_stream_t stream);
 
