@@ -66,9 +66,10 @@ TOWER_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so
 # Libraries added after those, by the same move once more: side_lib_names(), every_side_lib_names() and tower_lib_names() are each pinned by
 # the checks of the libraries before.  No name function is pinned to THIS dict, so a further library is one more name here.
 # "enroll": support sequences out of the stream pool's ring (StreamPool.enroll), C ABI in include/clipfsar_enroll.h.
+# "live_text": the EVAL_TEXT / COMBINE branches over grouped slot lists (LiveTextGallery), C ABI in include/clipfsar_live_text.h.
 LATER_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
                                  os.path.join(HERE, "build", name, "resource_usage.json"))
-                   for name in ("enroll",)}
+                   for name in ("enroll", "live_text")}
 
 
 def side_lib_names() -> list:

@@ -1,5 +1,5 @@
 // The exact-fp32 MFMA tile GEMM of the gallery libraries (otam_tile in otam_tile.h, the body of otam_gallery_kernel in gallery.hip, of
-// otam_indexed_kernel in live.hip and of otam_grouped_kernel in groups.hip; text_logits_kernel in gallery_text.hip):
+// otam_indexed_kernel in live.hip and of otam_grouped_kernel in groups.hip; text_logits_kernel in gallery_text.hip, text_logits_grouped_kernel in live_text.hip):
 // a 256-thread workgroup (4 waves) computes a TILE x TILE block of A[., E] x B[., E]^T with v_mfma_f32_16x16x4_f32 (an exact fp32 fmaf
 // chain per k step).  Both operands are staged through LDS in BK-float chunks, the next chunk's global loads in flight while the current
 // one is multiplied.  Wave w owns the 32 x 32 quarter (w >> 1, w & 1) as 2 x 2 MFMA tiles.  Inside a chunk, MFMA step s of lane half h

@@ -6,6 +6,7 @@
 
 #include "fp32_tile_gemm.h"
 #include "side_lib.h"
+#include "text_softmax.h"
 #include "../../include/clipfsar_gallery_text.h"
 
 namespace {
@@ -26,97 +27,27 @@ __global__ __launch_bounds__(128) void frame_mean_kernel(const float* __restrict
 
 // ---- zero-shot text logits of a gallery.  A workgroup (4 waves) owns 64 queries x 64 classes.
 //   GEMM: [NQ, E] x [C, E]^T, fp32_tile_gemm (fp32_tile_gemm.h) with one row per query / class.
-//   Epilogue: logits = scale * (dot / en / tn) into an LDS image of the tile (aliasing the staging buffers); then each wave stores
+//   Epilogue (text_tile_epilogue, text_softmax.h): logits = scale * (dot / en / tn) into an LDS image of the tile (aliasing the staging buffers); then each wave stores
 //   16 of its rows (lane = class column, coalesced) and reduces each row to the softmax partial (tile max, sum of expf(x - max)).
-constexpr int ILD = TILE + 1 /* logit image */;
-
 __global__ __launch_bounds__(256) void text_logits_kernel(const float* __restrict__ emb, const float* __restrict__ en,
                                                           const float* __restrict__ text, const float* __restrict__ tn,
                                                           const float* __restrict__ scale, float* __restrict__ logits,
                                                           float* __restrict__ partials, int NQ, int C, int E) {
-    static_assert(TILE * ILD <= 2 * TILE * SLD, "the logit image must fit into the staging buffers");
     __shared__ __attribute__((aligned(16))) float smem[2 * TILE * SLD];
     __shared__ float sen[TILE], stn[TILE];
     float* sA = smem;                                  // [TILE][SLD]
     float* sB = smem + TILE * SLD;                     // [TILE][SLD]
     float* img = smem;                                 // [TILE][ILD], after the K loop
     const int c0 = blockIdx.x * TILE, q0 = blockIdx.y * TILE;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int a_rows = min(TILE, NQ - q0), b_rows = min(TILE, C - c0);           // valid rows of each operand
     if (tid < TILE) sen[tid] = tid < a_rows ? en[q0 + tid] : 1.f;
     else if (tid < 2 * TILE) stn[tid - TILE] = tid - TILE < b_rows ? tn[c0 + tid - TILE] : 1.f;
 
     f32x4 acc[2][2];
     fp32_tile_gemm(emb, (size_t)q0, a_rows, text, (size_t)c0, b_rows, E, sA, sB, acc);   // ends with a barrier: the logit image overwrites the staging buffers
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, fr = lane & 15, fh = lane >> 4;
-    const float sc_ = scale[0];
-    // C/D map of the 16x16 MFMA: column = lane & 15, row = 4 (lane >> 4) + register
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int row = wm + 16 * mi + 4 * fh + g, col = wn + 16 * ni + fr;
-                img[row * ILD + col] = sc_ * (acc[mi][ni][g] / sen[row] / stn[col]);   // tail.hip:266's order, no eps
-            }
-    __syncthreads();
-    const int ntiles = gridDim.x;
-    const bool ok = lane < b_rows;
-    for (int r = wave; r < a_rows; r += 4) {                              // wave-uniform loop: 16 rows per wave
-        const float x = img[r * ILD + lane];
-        if (ok) logits[(size_t)(q0 + r) * C + c0 + lane] = x;
-        const float m = wave_max(ok ? x : -__builtin_inff());
-        const float s = wave_sum(ok ? expf(x - m) : 0.f);
-        if (lane == 0) {
-            float* p = partials + ((size_t)(q0 + r) * ntiles + blockIdx.x) * 2;
-            p[0] = m;
-            p[1] = s;
-        }
-    }
-}
-
-// ---- block-wide reductions of a 256-thread workgroup (red: 4 floats of LDS; safe to call back to back)
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the merged softmax statistics of one query row from its tile partials: M = max m_j, S = sum s_j expf(m_j - M)
-__device__ __forceinline__ void merge_partials(const float* __restrict__ pq, int ntiles, float* red, float& M, float& S) {
-    float m = -__builtin_inff();
-    for (int j = threadIdx.x; j < ntiles; j += 256) m = fmaxf(m, pq[2 * j]);
-    M = block_max(m, red);
-    float s = 0.f;
-    for (int j = threadIdx.x; j < ntiles; j += 256) s += pq[2 * j + 1] * expf(pq[2 * j] - M);
-    S = block_sum(s, red);
-}
-
-// f(x) over the C floats of a row: a scalar head up to 16-byte alignment, float4 loads, a scalar tail
-template <class F>
-__device__ __forceinline__ void row_pass4(const float* __restrict__ row, int C, F f) {
-    const int head = min(C, (int)(((16u - ((uint32_t)(uintptr_t)row & 15u)) & 15u) >> 2));
-    for (int c = threadIdx.x; c < head; c += 256) f(row[c]);
-    const int n4 = (C - head) >> 2;
-    const float4* r4 = reinterpret_cast<const float4*>(row + head);
-    for (int i = threadIdx.x; i < n4; i += 256) {
-        const float4 v = r4[i];
-        f(v.x);
-        f(v.y);
-        f(v.z);
-        f(v.w);
-    }
-    for (int c = head + 4 * n4 + threadIdx.x; c < C; c += 256) f(row[c]);
+    text_tile_epilogue(acc, img, sen, stn, scale[0], a_rows, b_rows, logits + (size_t)q0 * C + c0, (size_t)C,
+                       partials + ((size_t)q0 * gridDim.x + blockIdx.x) * 2, (size_t)gridDim.x * 2);
 }
 
 // ---- class-wide softmax: one workgroup per query (probs may alias logits: every element is read and written by the same thread)
@@ -124,11 +55,7 @@ __global__ __launch_bounds__(256) void text_softmax_kernel(const float* logits, 
                                                            int ntiles) {
     __shared__ float red[4];
     const size_t q = blockIdx.x;
-    float M, S;
-    merge_partials(partials + q * ntiles * 2, ntiles, red, M, S);
-    const float* x = logits + q * C;
-    float* o = probs + q * C;
-    for (int c = threadIdx.x; c < C; c += 256) o[c] = expf(x[c] - M) / S;
+    text_softmax_row(logits + q * C, partials + q * ntiles * 2, probs + q * C, C, ntiles, red);
 }
 
 // ---- COMBINE fusion (few_shot.py:2921-2928, combine_kernel's formula): one workgroup per query (out may alias logits)
@@ -136,22 +63,7 @@ __global__ __launch_bounds__(256) void text_combine_kernel(const float* logits, 
                                                            const float* __restrict__ visual, float* out, int C, int ntiles, float coff) {
     __shared__ float red[4];
     const size_t q = blockIdx.x;
-    float M, S;
-    merge_partials(partials + q * ntiles * 2, ntiles, red, M, S);
-    const float* v = visual + q * C;
-    float mv = -__builtin_inff();
-    row_pass4(v, C, [&](float x) { mv = fmaxf(mv, (8.0f + x) / 8.0f); });       // (8 - cum)/8 with cum = -v
-    const float Mv = block_max(mv, red);
-    float sv = 0.f;
-    row_pass4(v, C, [&](float x) { sv += expf((8.0f + x) / 8.0f - Mv); });
-    const float Sv = block_sum(sv, red);
-    const float* x = logits + q * C;
-    float* o = out + q * C;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        const float p = expf(x[c] - M) / S;
-        const float soft = expf((8.0f + v[c]) / 8.0f - Mv) / Sv;
-        o[c] = powf(p, coff) * powf(soft, 1.0f - coff);
-    }
+    text_combine_row(logits + q * C, partials + q * ntiles * 2, visual + q * C, out + q * C, C, ntiles, coff, red);
 }
 
 long long workspace_floats(int NQ, int C) { return (long long)NQ * ((C + TILE - 1) / TILE) * 2; }

@@ -1,5 +1,5 @@
-// Host error plumbing of the side libraries (gallery.hip, gallery_text.hip, stream.hip, pool.hip, ingest.hip, live.hip, groups.hip, lastblock.hip, enroll.hip;
-// through otam_tile.h for gallery.hip, live.hip and groups.hip): each is ONE translation unit, so these are internal-linkage items -- every library gets its own thread-local
+// Host error plumbing of the side libraries (gallery.hip, gallery_text.hip, stream.hip, pool.hip, ingest.hip, live.hip, groups.hip, lastblock.hip, enroll.hip, live_text.hip;
+// through otam_tile.h for gallery.hip, live.hip, groups.hip and live_text.hip): each is ONE translation unit, so these are internal-linkage items -- every library gets its own thread-local
 // message buffer and exports nothing of it.  (libclipfsar_hip.so shares cfsar_fail etc. across its translation units by linkage
 // instead: runtime.hip, which is not linked into the side libraries.)
 #pragma once

@@ -19,7 +19,8 @@ in place, and between growths (1.5 x when full) the store's address does not mov
 
 A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
 support sequences before context2) and its shot count: further shots continue the sum in cfsg_segment_mean's operation order
-(cfsl_accumulate).  Serves the default eval branch, like SupportGallery, and is accepted wherever one is (WindowStream, StreamPool).
+(cfsl_accumulate).  Serves the default eval branch, like SupportGallery, and is accepted wherever one is (WindowStream, StreamPool); the
+other two branches, EVAL_TEXT and COMBINE, over the same store are clip_fsar_amd.live_text_gallery.LiveTextGallery.
 """
 from __future__ import annotations
 
@@ -188,11 +189,7 @@ class GroupedLogits:
 class LiveGallery(_GalleryBase):
     def __init__(self, head, device="cuda", capacity=64):
         head = getattr(head, "head", head)                 # BaseVideoModel -> its CNN_OTAM_CLIPFSAR head
-        cfg = head.args
-        for flag in ("EVAL_TEXT", "COMBINE"):
-            if _flag(cfg.TRAIN, flag):
-                raise NotImplementedError("LiveGallery: TRAIN.%s is not supported -- the gallery serves the default eval branch (cosine + "
-                                          "OTAM of context2 features) only; use clip_fsar_amd.text_gallery.TextGallery for this branch" % flag)
+        self._check_branch(head.args)
         if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
             raise ValueError("LiveGallery: capacity must be an integer >= 1, got %r" % (capacity,))
         self._setup(head, device)
@@ -205,12 +202,19 @@ class LiveGallery(_GalleryBase):
         self._book = self._active = None
         self.clear()
 
+    def _check_branch(self, cfg):
+        """the eval branch the head's flags ask for is the one this gallery serves (LiveTextGallery serves the other two)"""
+        for flag in ("EVAL_TEXT", "COMBINE"):
+            if _flag(cfg.TRAIN, flag):
+                raise NotImplementedError("LiveGallery: TRAIN.%s is not supported -- the gallery serves the default eval branch (cosine + "
+                                          "OTAM of context2 features) only; use clip_fsar_amd.text_gallery.TextGallery for this branch" % flag)
+
     # ------------------------------------------------------------------ state
     def clear(self):
         """Drop every class (and bind to the head's current engine).  The store keeps its memory."""
         self._bind()
         version = 0 if self._book is None else self._book.version + bool(self._book.order)
-        cap = self._store["P"].shape[0] if self._store is not None else self._capacity
+        cap = self._store_cap() if self._store is not None else self._capacity
         self._install(new_book(cap)._replace(version=version))
 
     def _install(self, book):
@@ -242,24 +246,25 @@ class LiveGallery(_GalleryBase):
     def _rows(self):
         return self.T + 1                                  # rows of a support sequence, and of a slot of `sums`
 
+    def _store_cap(self):
+        return self._store["text"].shape[0]                # every store has a text row per slot
+
     def _alloc(self, cap):
         T, E, f = self.T, self.E, dict(device=self.dev, dtype=torch.float32)
-        return {"P": torch.empty(cap, T, E, **f), "pn": torch.empty(cap * T, **f), "text": torch.empty(cap, E, **f),
-                "sums": torch.empty(cap, self._rows(), E, **f)}
+        return {"P": torch.empty(cap, T, E, **f), "text": torch.empty(cap, E, **f), "sums": torch.empty(cap, self._rows(), E, **f),
+                "pn": torch.empty(cap * T, **f)}                 # in the order growth copies them
 
     def _ensure_store(self, cap):
         """the store with at least cap slots.  Growth copies the old slots once; the outgrown buffers are kept until the work queued on
         them (a classify in flight) is done."""
         self._retired = [(b, e) for b, e in self._retired if not e.query()]
         old = self._store
-        if old is not None and old["P"].shape[0] >= cap:
+        if old is not None and self._store_cap() >= cap:
             return old
         new = self._alloc(cap)
         if old is not None:
-            c0 = old["P"].shape[0]
-            for k in ("P", "text", "sums"):
-                new[k][:c0].copy_(old[k])
-            new["pn"][:c0 * self.T].copy_(old["pn"])
+            for k, t in old.items():                          # whatever the store holds: slots (or their rows) lead every buffer
+                new[k][:t.shape[0]].copy_(t)
             with torch.cuda.device(self.dev):
                 ev = torch.cuda.Event()
                 ev.record()
@@ -314,10 +319,14 @@ class LiveGallery(_GalleryBase):
         X0, seq_offs = sequences(trows)
         assert seq_offs == offs
         self._update_sequences(eng, X0, offs, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)])
-        st["text"].index_copy_(0, torch.tensor(plan.slots, device=self.dev), trows)
+        self._write_text_rows(st, plan.slots, trows)
         C0 = len(self._book.order)
         self._install(plan.book)
         return list(range(C0, C0 + len(plan.slots)))
+
+    def _write_text_rows(self, st, slots, trows):
+        """the new classes' text rows into their slots (LiveTextGallery: and their norms)"""
+        st["text"].index_copy_(0, torch.tensor(slots, device=self.dev), trows)
 
     def _shots_sequences(self, eng, plan, sequences):
         """the device work of further shots planned by plan_shots; sequences(trows) -> (X0, offs).  -> the classes' shot counts"""
@@ -338,11 +347,15 @@ class LiveGallery(_GalleryBase):
             class_of_video.reshape(-1).cpu() if isinstance(class_of_video, torch.Tensor) else class_of_video)]
         return [int(c) if isinstance(c, float) and c == int(c) else c for c in ids]
 
+    def _plan_shots(self, ids, book=None):
+        """plan_shots on `book`, default the gallery's (StreamPool.enroll_windows plans a whole call on a book of its own)"""
+        return plan_shots(self._book if book is None else book, ids, self._name)
+
     def _add_shots(self, eng, src, class_of_video, sequences_of):
         ids = self._shot_ids(class_of_video)
         if len(ids) != src.shape[0]:
             raise ValueError("%s: %d videos but %d class ids" % (self._name, src.shape[0], len(ids)))
-        plan = plan_shots(self._book, ids, self._name)
+        plan = self._plan_shots(ids)
         return self._shots_sequences(eng, plan, lambda trows: sequences_of(src, ids, plan.classes, trows))
 
     def add_classes(self, videos, class_of_video, text=None):
@@ -455,6 +468,13 @@ class LiveGallery(_GalleryBase):
                                                                                               grhip.MAX_GROUPS))
         return plan
 
+    def _score_groups(self, eng, feats, n, ws, cols, rows, out, n_out):
+        """a chunk of n clips under the table `rows` (chunk_groups) and its part of the slot lists -> out [n_out]: the eval branch"""
+        T, st = self.T, self._store
+        Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
+        ghip.row_norms(Xq, ws["qn"])
+        grhip.otam_grouped(Xq, ws["qn"], st["P"], st["pn"], cols, out, self._upload_groups(rows), n_out, LAMBDA, self.single_direct)
+
     def _classify_groups(self, src, tower, counts, classes):
         eng = self._fresh_engine()
         plan = self._plan_groups(counts, classes)             # every error before the device is touched
@@ -466,7 +486,7 @@ class LiveGallery(_GalleryBase):
         key = tuple(plan.slots)
         if self._group_cols[0] != key:
             self._group_cols = (key, torch.tensor(plan.slots, device=self.dev, dtype=torch.int32))
-        cols, st, T = self._group_cols[1], self._store, self.T
+        cols, T = self._group_cols[1], self.T
         out = torch.empty(plan.n_out, device=self.dev, dtype=torch.float32)
         chunk = max(1, eng.max_frames // T)                   # _GalleryBase._classify's chunks: a chunk may start and end inside groups
         for q0 in range(0, N, chunk):
@@ -479,10 +499,7 @@ class LiveGallery(_GalleryBase):
                 self._features(eng, src[q0:q1], feats)
             rows, (c_lo, c_hi), out_lo = chunk_groups(plan.rows, q0, q1, T)
             n_out = sum(r[grhip.NQ] * r[grhip.NC] for r in rows)
-            Xq = self._context2(eng, feats, n, T, n_a_form=True)[:n * T].view(n, T, self.E)      # :2948
-            ghip.row_norms(Xq, ws["qn"])
-            grhip.otam_grouped(Xq, ws["qn"], st["P"], st["pn"], cols[c_lo:c_hi], out[out_lo:out_lo + n_out], self._upload_groups(rows),
-                               n_out, LAMBDA, self.single_direct)
+            self._score_groups(eng, feats, n, ws, cols[c_lo:c_hi], rows, out[out_lo:out_lo + n_out], n_out)
         offsets = [r[grhip.OUT0] for r in plan.rows] + [plan.n_out]
         return GroupedLogits(out, offsets, [r[grhip.NC] for r in plan.rows], [r[grhip.NQ] for r in plan.rows]), plan
 
@@ -556,7 +573,7 @@ class LiveGallery(_GalleryBase):
             raise ValueError("LiveGallery.load_state_dict: a class id appears twice")
         self._bind()
         old_version = self._book.version
-        book = new_book(max(self._capacity, C, self._store["P"].shape[0] if self._store is not None else 0))
+        book = new_book(max(self._capacity, C, self._store_cap() if self._store is not None else 0))
         if C:
             plan = plan_add(book, ids, None, self._name)
             book = plan.book._replace(shots=dict(zip(ids, counts if sums is not None else [0] * C)))

@@ -480,7 +480,6 @@ class StreamPool:
         the first of a new class (add_classes' rules; its text from TEST.CLASS_NAME or from `text`).  Several windows of one class are its
         shots in the order given.  The windows' tower rows are read out of the ring -- one launch for the new classes, one for the further
         shots -- and the tower does not run.  Every error is raised before any launch and leaves the gallery as it was."""
-        from .live_gallery import plan_shots
         g = self._enrolling_gallery()
         eng = g._fresh_engine()
         items = list(items) if isinstance(items, (list, tuple)) else None
@@ -500,7 +499,7 @@ class StreamPool:
         new = [i for i, c in enumerate(ids) if c not in book.slot_of]
         shot_plan = add = None
         if known:
-            shot_plan = plan_shots(book, [ids[i] for i in known], g._name)
+            shot_plan = g._plan_shots([ids[i] for i in known], book)
             book = shot_plan.book
         if new:
             new_ids = list(dict.fromkeys(ids[i] for i in new))
