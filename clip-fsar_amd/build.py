@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS, LATER_SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -36,65 +36,21 @@ NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
 # The side libraries, in the order they are built: the support gallery, its text half (EVAL_TEXT / COMBINE), the window streams' ring,
-# gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, and the live gallery; C ABI of each in
-# include/clipfsar_<name>.h.  Each is ONE source, csrc/<name>.hip, compiled with the product FLAGS and the fence into a library of its own
-# beside libclipfsar_hip.so (the pinned export sets stay apart), stale when a file its source reaches through #include is newer, with its
-# own resource report (build/resource_usage.json stays the product library's).  A further library is one more name here.
+# gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, the live gallery, grouped scoring, the last
+# ViT block's class-token attention without its K | V projection, enrolment out of the stream pool's ring, and the text branches over
+# grouped slot lists; C ABI of each in include/clipfsar_<name>.h.  Each is ONE source, csrc/<name>.hip, compiled with the product FLAGS and
+# the fence into a library of its own beside libclipfsar_hip.so (the pinned export sets stay apart), stale when a file its source reaches
+# through #include is newer, with its own resource report (build/resource_usage.json stays the product library's).  This dict is the only
+# registry (when a library is loaded is its binding's business, not the build's): a further library is one more name here, and one more
+# row in the table of tests/_abi.py.
 SideLib = collections.namedtuple("SideLib", "source lib usage")
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
                            os.path.join(HERE, "build", name, "resource_usage.json"))
-             for name in ("gallery", "gallery_text", "stream", "pool", "ingest", "live")}
-
-
-# Libraries added after the six: the same SideLib tuple, recipe and call sites, in a dict of their own.  SIDE_LIBS and side_lib_names()
-# are what the earlier libraries' checks enumerate as "the side libraries" (each one's exports and kernel names are compared against
-# exactly those), so a library they were not written against is registered here, where every_side_lib_names(), build_side(), _side_deps(),
-# _product_deps() and build() find it, and not there.  "groups": grouped scoring, C ABI in include/clipfsar_groups.h.
-MORE_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                                os.path.join(HERE, "build", name, "resource_usage.json"))
-                  for name in ("groups",)}
-
-
-# Libraries of the image tower (the engine's forward loads them on first use), by the same move: the same SideLib tuple, recipe and call
-# sites in a third dict, because side_lib_names() and every_side_lib_names() are pinned by the checks of the libraries before them too.
-# "lastblock": the last block's class-token attention without its K | V projection, C ABI in include/clipfsar_lastblock.h.
-TOWER_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                            os.path.join(HERE, "build", name, "resource_usage.json"))
-              for name in ("lastblock",)}
-
-
-# Libraries added after those, by the same move once more: side_lib_names(), every_side_lib_names() and tower_lib_names() are each pinned by
-# the checks of the libraries before.  No name function is pinned to THIS dict, so a further library is one more name here.
-# "enroll": support sequences out of the stream pool's ring (StreamPool.enroll), C ABI in include/clipfsar_enroll.h.
-# "live_text": the EVAL_TEXT / COMBINE branches over grouped slot lists (LiveTextGallery), C ABI in include/clipfsar_live_text.h.
-LATER_SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
-                                 os.path.join(HERE, "build", name, "resource_usage.json"))
-                   for name in ("enroll", "live_text")}
+             for name in ("gallery", "gallery_text", "stream", "pool", "ingest", "live", "groups", "lastblock", "enroll", "live_text")}
 
 
 def side_lib_names() -> list:
     return list(SIDE_LIBS)
-
-
-def every_side_lib_names() -> list:
-    """side_lib_names() and the libraries of MORE_SIDE_LIBS, in build order"""
-    return list(SIDE_LIBS) + list(MORE_SIDE_LIBS)
-
-
-def tower_lib_names() -> list:
-    return list(TOWER_LIBS)
-
-
-def _all_lib_names() -> list:
-    """every library built beside the product library, in build order"""
-    return every_side_lib_names() + tower_lib_names() + list(LATER_SIDE_LIBS)
-
-
-def _side_lib(name) -> SideLib:
-    for libs in (SIDE_LIBS, MORE_SIDE_LIBS, LATER_SIDE_LIBS):
-        if name in libs:
-            return libs[name]
-    return TOWER_LIBS[name]
 
 
 def _parse_usage(text: str) -> dict:
@@ -130,13 +86,13 @@ def _includes(path, seen=None) -> set:
 
 
 def _side_deps(name) -> list:
-    return sorted(_includes(os.path.join(CSRC, _side_lib(name).source))) + [os.path.abspath(__file__)]
+    return sorted(_includes(os.path.join(CSRC, SIDE_LIBS[name].source))) + [os.path.abspath(__file__)]
 
 
 def _product_deps() -> list:
     """every file of csrc/ that is not a side library's source or a header only side libraries include"""
     ours = set().union(*(_includes(os.path.join(CSRC, s)) for s in SOURCES))
-    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in map(_side_lib, _all_lib_names()))) - ours
+    side_only = set().union(*(_includes(os.path.join(CSRC, sl.source)) for sl in SIDE_LIBS.values())) - ours
     return [p for p in (os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))) if p not in side_only] + [
         os.path.join(os.path.dirname(HERE), "include", "clipfsar_hip.h"), os.path.abspath(__file__)]
 
@@ -180,9 +136,9 @@ def _link(lib, objs, usage, usage_path, verbose) -> str:
 
 
 def build_side(name, force: bool = False, verbose: bool = True) -> str:
-    """a side library (SIDE_LIBS, MORE_SIDE_LIBS, TOWER_LIBS or LATER_SIDE_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
+    """a side library (a name of SIDE_LIBS): its one source -> its own library with the product FLAGS and the packed-fp32 fence,
     resource report -> .usage"""
-    sl = _side_lib(name)
+    sl = SIDE_LIBS[name]
     if not force and not _stale(sl.lib, _side_deps(name)):
         return sl.lib
     bdir = os.path.dirname(sl.usage)
@@ -195,7 +151,7 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
     The product build also builds the side libraries (build_side)."""
     if not (dev or packed or variant):
-        for name in _all_lib_names():
+        for name in side_lib_names():
             build_side(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):

@@ -25,7 +25,7 @@ _lib = None
 
 _c_int, _c_p = ctypes.c_int, ctypes.c_void_p
 
-# symbol -> argtypes; must match include/clipfsar_enroll.h (tests/test_enroll_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_enroll.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cfen_version": [],
     "cfen_abi_version": [],

@@ -20,7 +20,7 @@ _lib = None
 
 _c_int, _c_p, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 
-# symbol -> argtypes; must match include/clipfsar_gallery.h (tests/test_gallery_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_gallery.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cfsg_version": [],
     "cfsg_abi_version": [],

@@ -29,7 +29,7 @@ _lib = None
 
 _c_int, _c_p, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 
-# symbol -> argtypes; must match include/clipfsar_groups.h (tests/test_groups_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_groups.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cfgr_version": [],
     "cfgr_abi_version": [],

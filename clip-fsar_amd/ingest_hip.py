@@ -27,7 +27,7 @@ _lib = None
 
 _c_int, _c_i64, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 
-# symbol -> argtypes; must match include/clipfsar_ingest.h (tests/test_ingest_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_ingest.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cfsi_version": [],
     "cfsi_abi_version": [],

@@ -28,7 +28,7 @@ _lib = None
 
 _c_int, _c_p, _c_f = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 
-# symbol -> argtypes; must match include/clipfsar_live_text.h (tests/test_live_text_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_live_text.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cflt_version": [],
     "cflt_abi_version": [],

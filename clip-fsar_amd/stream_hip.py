@@ -20,7 +20,7 @@ _lib = None
 
 _c_int, _c_p, _c_f, _c_i64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_int64
 
-# symbol -> argtypes; must match include/clipfsar_stream.h (tests/test_stream_abi.py cross-checks against the header text)
+# symbol -> argtypes; must match include/clipfsar_stream.h (tests/test_build_recipe.py cross-checks against the header text)
 SIGNATURES = {
     "cfss_version": [],
     "cfss_abi_version": [],

@@ -1,9 +1,8 @@
-"""CPU: the enrolment library (libclipfsar_enroll.so, include/clipfsar_enroll.h) builds beside the other nine from a registry of its own,
-exports exactly its header, checks its ABI revision at load, validates its enrolment list without a GPU, keeps its kernels out of scratch
-and is stale exactly when its own files or the headers it reaches change; pool.plan_enroll against a brute-force ring; misuse of
-StreamPool.enroll / enroll_windows and of LiveGallery's registration from features on a stub head."""
+"""CPU: the enrolment library (libclipfsar_enroll.so, include/clipfsar_enroll.h) validates its enrolment list without a GPU and takes its copy-
+kernel plumbing from ring_rows.h; pool.plan_enroll against a brute-force ring; misuse of StreamPool.enroll / enroll_windows and of
+LiveGallery's registration from features on a stub head.  Its exports, kernels and place in the build are checked with every library's in
+tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -11,37 +10,28 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _prototypes, check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_enroll.h")
-SIX = ["gallery", "gallery_text", "stream", "pool", "ingest", "live"]
 
 
 @pytest.fixture(scope="module")
 def elib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all ten libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import enroll_hip
     return enroll_hip.lib()
 
 
-# ------------------------------------------------------------------ the library and its place in the build
+# ------------------------------------------------------------------ what is particular to this library's header and source
 def test_header_exported_exactly_and_arity_matches(elib):
+    check_exports(lib_row("enroll"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import enroll_hip as eh
     from clip_fsar_amd import pool_hip as ph
     protos = _prototypes(HEADER, "cfen_")
-    assert set(protos) == {"cfen_version", "cfen_abi_version", "cfen_last_error", "cfen_ring_sequences"}, protos
-    assert _exported(eh.LIB_PATH) == set(protos), sorted(_exported(eh.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfen_last_error":
-            continue
-        assert len(eh.SIGNATURES[name]) == nargs, (name, len(eh.SIGNATURES[name]), nargs)
-    assert set(eh.SIGNATURES) | {"cfen_last_error"} == set(protos)
     assert protos["cfen_ring_sequences"] == 13
-    assert elib.cfen_abi_version() == eh.ABI_VERSION and elib.cfen_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFEN_ABI_VERSION (\d+)", text).group(1)) == eh.ABI_VERSION
     assert int(re.search(r"#define CFEN_TABLE_COLS (\d+)", text).group(1)) == eh.TABLE_COLS == 4
     for i, col in enumerate(("SLOT", "POS", "CLS", "PAD")):                       # the binding's column order is the header's
         assert int(re.search(r"#define CFEN_%s (\d+)" % col, text).group(1)) == getattr(eh, col) == i
@@ -51,84 +41,15 @@ def test_header_exported_exactly_and_arity_matches(elib):
 
 
 def test_abi_version_is_checked_at_load(elib, monkeypatch):
-    from clip_fsar_amd import enroll_hip as eh
-    monkeypatch.setattr(eh, "_lib", None)
-    monkeypatch.setattr(eh, "ABI_VERSION", eh.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        eh.lib()
-    monkeypatch.setattr(eh, "LIB_PATH", eh.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        eh.lib()
+    check_abi_at_load(lib_row("enroll"), monkeypatch)
 
 
-def test_the_other_nine_libraries_export_nothing_of_it(elib):
-    from clip_fsar_amd import (enroll_hip, gallery_hip, gallery_text_hip, groups_hip, hip, ingest_hip, lastblock_hip, live_hip, pool_hip,
-                               stream_hip)
-    ours = _exported(enroll_hip.LIB_PATH)
-    assert ours and all(s.startswith("cfen_") for s in ours), sorted(ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip, groups_hip, lastblock_hip):
-        assert not any(s.startswith("cfen_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(elib):
+def test_the_source_takes_its_copy_kernel_plumbing_from_ring_rows():
     from clip_fsar_amd import build as b
-    sl = b._side_lib("enroll")
-    if not os.path.exists(sl.usage):
-        b.build_side("enroll", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    assert len(usage) == 2 and all("ring_sequences_kernel" in n for n in usage), sorted(usage)      # 16-byte and 4-byte pieces
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "enroll.hip" and sl.source not in b.SOURCES and sl.lib.endswith(os.sep + "libclipfsar_enroll.so")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "enroll", "resource_usage.json"))
-    others = [b.USAGE] + [b._side_lib(n).usage for n in SIX + ["groups", "lastblock"]]
-    assert len(set(others)) == 9 and sl.usage not in others
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-    src = open(os.path.join(b.CSRC, sl.source)).read()
+    src = open(os.path.join(b.CSRC, b.SIDE_LIBS["enroll"].source)).read()
     for body in ("__shared__", "asm", "struct Piece", "MAX_BLOCKS =", "MAX_ITEMS =", "unsigned blocks_for", "thread_local"):
         assert body not in src, body
     assert '#include "ring_rows.h"' in src and "Piece<VEC>" in src and "blocks_for(" in src
-
-
-def test_a_fourth_registry_and_the_three_pinned_ones(elib):
-    from clip_fsar_amd import build as b
-    registries = [d for d in vars(b).values() if isinstance(d, dict) and d and all(isinstance(v, b.SideLib) for v in d.values())]
-    assert len(registries) == 4
-    new = [d for d in registries if "enroll" in d]
-    assert len(new) == 1 and new[0] is not b.SIDE_LIBS and new[0] is not b.MORE_SIDE_LIBS and new[0] is not b.TOWER_LIBS
-    assert not set(new[0]) & (set(b.SIDE_LIBS) | set(b.MORE_SIDE_LIBS) | set(b.TOWER_LIBS))
-    assert b.side_lib_names() == SIX and b.every_side_lib_names() == SIX + ["groups"] and b.tower_lib_names() == ["lastblock"]
-    assert list(b.SIDE_LIBS) == SIX and list(b.MORE_SIDE_LIBS) == ["groups"] and list(b.TOWER_LIBS) == ["lastblock"]
-    assert b._all_lib_names() == SIX + ["groups", "lastblock"] + list(new[0])
-    assert b._side_lib("enroll") is new[0]["enroll"]
-    with pytest.raises(KeyError):
-        b._side_lib("nobody")
-    for name in b._all_lib_names():                 # the fixture ran build(): every library of the four registries is there
-        assert os.path.exists(b._side_lib(name).lib), name
-
-
-def test_an_edited_file_makes_exactly_the_libraries_that_reach_it_stale(monkeypatch):
-    from clip_fsar_amd import build as b
-    names = b._all_lib_names()
-    stale_by_file = {
-        "enroll.hip": {"enroll"},
-        "clipfsar_enroll.h": {"enroll"},
-        "clipfsar_pool.h": {"pool", "enroll"},      # the enrolment header takes CFSP_MAX_T from it
-        "ring_rows.h": {"stream", "pool", "enroll"},
-        "side_lib.h": set(names),
-        "common.h": set(names) | {"product"},
-        "pool.hip": {"pool"},
-        "tail.hip": {"product"},
-    }
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    for edited, want in sorted(stale_by_file.items()):
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + edited) else 1.0)
-        stale = {"product"} if b._stale(b.LIB, b._product_deps()) else set()
-        stale |= {n for n in names if b._stale(b._side_lib(n).lib, b._side_deps(n))}
-        assert stale == want, edited
-    assert os.path.join(b.CSRC, "enroll.hip") not in b._product_deps()
 
 
 # ------------------------------------------------------------------ the enrolment list, without a GPU

@@ -1,48 +1,24 @@
-"""CPU: the text half of the support gallery (libclipfsar_gallery_text.so, include/clipfsar_gallery_text.h) builds beside the other two
-libraries, exports exactly its header, validates arguments without a GPU, keeps its kernels out of scratch; TextGallery resolves its mode
-from the head's flags as the head does."""
+"""CPU: the text half of the support gallery (libclipfsar_gallery_text.so, include/clipfsar_gallery_text.h) sizes its workspace and validates
+arguments without a GPU; TextGallery resolves its mode from the head's flags as the head does.  Its exports, kernels and place in the build
+are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
-import os
-import re
 from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _other_reports, _prototypes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "clipfsar_gallery_text.h")
+from _abi import check_exports, lib_row
 
 
 @pytest.fixture(scope="module")
 def tlib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all three libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import gallery_text_hip
     return gallery_text_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(tlib):
-    from clip_fsar_amd import gallery_text_hip as gt
-    protos = _prototypes(HEADER, "cfgt_")
-    assert len(protos) == 8, protos
-    assert _exported(gt.LIB_PATH) == set(protos), sorted(_exported(gt.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfgt_last_error":
-            continue
-        assert len(gt.SIGNATURES[name]) == nargs, (name, len(gt.SIGNATURES[name]), nargs)
-    assert set(gt.SIGNATURES) | {"cfgt_last_error"} == set(protos)
-    assert tlib.cfgt_abi_version() == gt.ABI_VERSION and tlib.cfgt_version() >= 100
-    m = re.search(r"#define CFGT_ABI_VERSION (\d+)", open(HEADER).read())
-    assert int(m.group(1)) == gt.ABI_VERSION
-
-
-def test_other_libraries_keep_their_export_sets(tlib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip
-    ours = _exported(gallery_text_hip.LIB_PATH)
-    assert not any(s.startswith(("cfsg_", "cfsar_")) for s in ours)
-    assert not any(s.startswith("cfgt_") for s in _exported(gallery_hip.LIB_PATH))
+    check_exports(lib_row("gallery_text"))
 
 
 def test_workspace_size(tlib):
@@ -82,23 +58,6 @@ def test_python_wrappers_reject_cpu_tensors(tlib):
         gt.frame_mean(torch.zeros(2, 4, 8), torch.zeros(2, 8))
     with pytest.raises(RuntimeError, match="shape"):
         gt.frame_mean(torch.zeros(2, 4, 8), torch.zeros(2, 9))
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(tlib):
-    from clip_fsar_amd import build as b
-    if not os.path.exists(b.SIDE_LIBS["gallery_text"].usage):
-        b.build_side("gallery_text", force=True, verbose=False)
-    usage = json.load(open(b.SIDE_LIBS["gallery_text"].usage))
-    names = sorted(usage)
-    for k in ("frame_mean_kernel", "text_logits_kernel", "text_softmax_kernel", "text_combine_kernel"):
-        assert sum(k in n for n in names) == 1, (k, names)
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0, (n, u)
-        assert "otam_gallery_kernel" not in n, n
-    assert b.SIDE_LIBS["gallery_text"].source not in b.SOURCES
-    for other in _other_reports("gallery_text"):
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other)))
 
 
 # ------------------------------------------------------------------ mode resolution (no GPU: a stub head)

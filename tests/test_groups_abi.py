@@ -1,9 +1,7 @@
-"""CPU: the grouped-scoring library (libclipfsar_groups.so, include/clipfsar_groups.h) builds beside the other seven libraries from a
-registry of its own, exports exactly its header, validates its descriptor table without a GPU, keeps its kernels out of scratch and is
-stale exactly when its own files or the headers it shares change; LiveGallery.plan_groups against a list model; misuse of the grouped
-calls of LiveGallery and StreamPool on a stub head."""
+"""CPU: the grouped-scoring library (libclipfsar_groups.so, include/clipfsar_groups.h) validates its descriptor table without a GPU;
+LiveGallery.plan_groups against a list model; misuse of the grouped calls of LiveGallery and StreamPool on a stub head.  Its exports,
+kernels and place in the build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -11,35 +9,26 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _prototypes, check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_groups.h")
-SIX = ["gallery", "gallery_text", "stream", "pool", "ingest", "live"]
 
 
 @pytest.fixture(scope="module")
 def glib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all eight libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import groups_hip
     return groups_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(glib):
+    check_exports(lib_row("groups"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import groups_hip as gh
     protos = _prototypes(HEADER, "cfgr_")
-    assert set(protos) == {"cfgr_version", "cfgr_abi_version", "cfgr_last_error", "cfgr_otam_grouped", "cfgr_topk_grouped"}, protos
-    assert _exported(gh.LIB_PATH) == set(protos), sorted(_exported(gh.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfgr_last_error":
-            continue
-        assert len(gh.SIGNATURES[name]) == nargs, (name, len(gh.SIGNATURES[name]), nargs)
-    assert set(gh.SIGNATURES) | {"cfgr_last_error"} == set(protos)
     assert protos["cfgr_otam_grouped"] == 18 and protos["cfgr_topk_grouped"] == 10
-    assert glib.cfgr_abi_version() == gh.ABI_VERSION and glib.cfgr_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFGR_ABI_VERSION (\d+)", text).group(1)) == gh.ABI_VERSION
     assert int(re.search(r"#define CFGR_MAX_T (\d+)", text).group(1)) == gh.MAX_T == 32
     assert int(re.search(r"#define CFGR_MAX_GROUPS (\d+)", text).group(1)) == gh.MAX_GROUPS
     assert int(re.search(r"#define CFGR_TOPK_MAX (\d+)", text).group(1)) == gh.TOPK_MAX == 16
@@ -49,92 +38,7 @@ def test_header_exported_exactly_and_arity_matches(glib):
 
 
 def test_abi_version_is_checked_at_load(glib, monkeypatch):
-    from clip_fsar_amd import groups_hip as gh
-    monkeypatch.setattr(gh, "_lib", None)
-    monkeypatch.setattr(gh, "ABI_VERSION", gh.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        gh.lib()
-    monkeypatch.setattr(gh, "LIB_PATH", gh.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        gh.lib()
-
-
-def test_the_other_seven_libraries_export_nothing_of_it(glib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, groups_hip, hip, ingest_hip, live_hip, pool_hip, stream_hip
-    ours = _exported(groups_hip.LIB_PATH)
-    assert ours and all(s.startswith("cfgr_") for s in ours), sorted(ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip):
-        assert not any(s.startswith("cfgr_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(glib):
-    from clip_fsar_amd import build as b
-    sl = b.MORE_SIDE_LIBS["groups"]
-    if not os.path.exists(sl.usage):
-        b.build_side("groups", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    assert len(names) == 4 and len([n for n in names if "otam_grouped" in n]) == 3, names      # T = 8, T = 16, run-time T
-    assert any("topk_grouped_kernel" in n for n in names)
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "groups.hip" and sl.source not in b.SOURCES and sl.lib.endswith(os.sep + "libclipfsar_groups.so")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "groups", "resource_usage.json"))
-    others = [b.USAGE] + [b.SIDE_LIBS[n].usage for n in SIX]
-    assert len(set(others)) == 7 and sl.usage not in others
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-
-
-def test_two_registries_six_names_and_seven():
-    from clip_fsar_amd import build as b
-    assert list(b.SIDE_LIBS) == SIX and b.side_lib_names() == SIX
-    assert list(b.MORE_SIDE_LIBS) == ["groups"] and b.every_side_lib_names() == SIX + ["groups"]
-    assert not set(b.SIDE_LIBS) & set(b.MORE_SIDE_LIBS)
-    with pytest.raises(KeyError):
-        b._side_deps("nobody")
-
-
-def test_an_edited_file_makes_exactly_the_libraries_that_reach_it_stale(monkeypatch):
-    from clip_fsar_amd import build as b
-    names = b.every_side_lib_names()
-    stale_by_file = {
-        "groups.hip": {"groups"},
-        "clipfsar_groups.h": {"groups"},
-        "otam_tile.h": {"gallery", "live", "groups"},
-        "topk_wave.h": {"gallery", "groups"},
-        "fp32_tile_gemm.h": {"gallery", "gallery_text", "live", "groups"},
-        "side_lib.h": set(names),
-        "live.hip": {"live"},
-        "tail.hip": {"product"},
-    }
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    for edited, want in sorted(stale_by_file.items()):
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + edited) else 1.0)
-        stale = {"product"} if b._stale(b.LIB, b._product_deps()) else set()
-        stale |= {n for n in names if b._stale(b._side_lib(n).lib, b._side_deps(n))}
-        assert stale == want, edited
-    deps = b._product_deps()
-    for f in ("groups.hip", "topk_wave.h", "otam_tile.h"):
-        assert os.path.join(b.CSRC, f) not in deps, f
-
-
-def test_the_tile_body_and_the_slot_arithmetic_have_one_copy():
-    from clip_fsar_amd import build as b
-    src = lambda name: open(os.path.join(b.CSRC, name)).read()
-    tile, groups, live = src("otam_tile.h"), src("groups.hip"), src("live.hip")
-    assert tile.count("void otam_tile_at(") == 1 and tile.count("otam_tile_at<TT>(") == 1 and "blockIdx" in tile
-    assert groups.count("otam_tile_at<TT>(") == 1 and '#include "otam_tile.h"' in groups and "LookedUpRow{" in groups
-    for body in ("__builtin_amdgcn_mfma", "fp32_tile_gemm_rows(", "otam_dp<", "0.01f", "extern __shared__", "asm"):
-        assert body not in groups, body
-    assert tile.count("slot = cols[c0 + j]") == 1                                 # the slot arithmetic: otam_tile.h alone
-    for text in (groups, live):
-        assert "store_slot_row(" in text and "store_slot_norm(" in text and "cols[c0 + j]" not in text
-    topk = src("topk_wave.h")
-    assert topk.count("__shfl_xor(bv") == 1
-    for text in (groups, src("gallery.hip")):
-        assert text.count("topk_wave(") == 1 and "__shfl_xor" not in text
+    check_abi_at_load(lib_row("groups"), monkeypatch)
 
 
 # ------------------------------------------------------------------ table validation, without a GPU

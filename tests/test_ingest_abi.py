@@ -1,15 +1,14 @@
-"""CPU: the frame-ingest library (libclipfsar_ingest.so, include/clipfsar_ingest.h) builds beside the other five libraries, exports exactly
-its header, validates arguments and descriptor tables without a GPU, keeps its kernels out of scratch, and is stale exactly when its own
-files or the shared transform header change; FrameIngest, StreamPool.push_u8 and WindowStream.push_u8 reject misuse before any device work."""
+"""CPU: the frame-ingest library (libclipfsar_ingest.so, include/clipfsar_ingest.h) validates arguments and descriptor tables without a GPU;
+FrameIngest, StreamPool.push_u8 and WindowStream.push_u8 reject misuse before any device work.  Its exports, kernels and place in the build
+are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import re
 from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _other_reports, _prototypes
+from _abi import check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_ingest.h")
@@ -18,24 +17,15 @@ HEADER = os.path.join(ROOT, "include", "clipfsar_ingest.h")
 @pytest.fixture(scope="module")
 def ilib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all six libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import ingest_hip
     return ingest_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(ilib):
+    check_exports(lib_row("ingest"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import ingest_hip as ih
-    protos = _prototypes(HEADER, "cfsi_")
-    assert set(protos) == {"cfsi_version", "cfsi_abi_version", "cfsi_last_error", "cfsi_transform_frames"}, protos
-    assert _exported(ih.LIB_PATH) == set(protos), sorted(_exported(ih.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfsi_last_error":
-            continue
-        assert len(ih.SIGNATURES[name]) == nargs, (name, len(ih.SIGNATURES[name]), nargs)
-    assert set(ih.SIGNATURES) | {"cfsi_last_error"} == set(protos)
-    assert ilib.cfsi_abi_version() == ih.ABI_VERSION and ilib.cfsi_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFSI_ABI_VERSION (\d+)", text).group(1)) == ih.ABI_VERSION
     assert int(re.search(r"#define CFSI_MAX_GROUPS (\d+)", text).group(1)) == ih.MAX_GROUPS
     assert int(re.search(r"#define CFSI_SRC_ALIGN (\d+)", text).group(1)) == ih.SRC_ALIGN == 16
     assert int(re.search(r"#define CFSI_TABLE_COLS (\d+)", text).group(1)) == ih.TABLE_COLS == 9
@@ -45,48 +35,7 @@ def test_header_exported_exactly_and_arity_matches(ilib):
 
 
 def test_abi_version_is_checked_at_load(ilib, monkeypatch):
-    from clip_fsar_amd import ingest_hip as ih
-    monkeypatch.setattr(ih, "_lib", None)
-    monkeypatch.setattr(ih, "ABI_VERSION", ih.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        ih.lib()
-    monkeypatch.setattr(ih, "LIB_PATH", ih.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        ih.lib()
-
-
-def test_the_other_five_libraries_export_nothing_of_it(ilib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, ingest_hip, pool_hip, stream_hip
-    ours = _exported(ingest_hip.LIB_PATH)
-    assert not any(s.startswith(("cfsg_", "cfsar_", "cfgt_", "cfss_", "cfsp_")) for s in ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip):
-        assert not any(s.startswith("cfsi_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(ilib):
-    from clip_fsar_amd import build as b
-    sl = b.SIDE_LIBS["ingest"]
-    if not os.path.exists(sl.usage):
-        b.build_side("ingest", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    assert len(names) == 2 and all("ingest_transform_kernel" in n for n in names), names          # 16-byte and 4-byte stores
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source not in b.SOURCES
-    others = _other_reports("ingest")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "ingest", "resource_usage.json"))
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-
-
-def test_build_products_are_git_ignored():
-    from clip_fsar_amd import build as b
-    patterns = set(open(os.path.join(ROOT, ".gitignore")).read().split())
-    assert {"*.so", "*.o", "build/"} <= patterns
-    sl = b.SIDE_LIBS["ingest"]
-    assert sl.lib.endswith(os.sep + "libclipfsar_ingest.so") and os.sep + "build" + os.sep in sl.usage
+    check_abi_at_load(lib_row("ingest"), monkeypatch)
 
 
 # ------------------------------------------------------------------ validation, without a GPU

@@ -1,43 +1,31 @@
-"""CPU: the last-block library (libclipfsar_lastblock.so, include/clipfsar_lastblock.h) builds beside the other eight from a third registry
-(build.TOWER_LIBS), exports exactly its header, checks its ABI revision at load, validates its arguments without a GPU, keeps its kernels
-out of scratch and is stale exactly when its own files or the headers it shares change."""
+"""CPU: the last-block library (libclipfsar_lastblock.so, include/clipfsar_lastblock.h) validates its arguments without a GPU and its wrappers
+reject misuse.  Its exports, kernels and place in the build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import re
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _prototypes, check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_lastblock.h")
-SEVEN = ["gallery", "gallery_text", "stream", "pool", "ingest", "live", "groups"]
 
 
 @pytest.fixture(scope="module")
 def llib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all nine libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import lastblock_hip
     return lastblock_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(llib):
+    check_exports(lib_row("lastblock"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import lastblock_hip as lb
     protos = _prototypes(HEADER, "cflb_")
-    assert set(protos) == {"cflb_version", "cflb_abi_version", "cflb_last_error", "cflb_key_fold", "cflb_class_attend",
-                           "cflb_value_fold"}, protos
-    assert _exported(lb.LIB_PATH) == set(protos), sorted(_exported(lb.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cflb_last_error":
-            continue
-        assert len(lb.SIGNATURES[name]) == nargs, (name, len(lb.SIGNATURES[name]), nargs)
-    assert set(lb.SIGNATURES) | {"cflb_last_error"} == set(protos)
     assert protos["cflb_key_fold"] == 9 and protos["cflb_class_attend"] == 13 and protos["cflb_value_fold"] == 9
-    assert llib.cflb_abi_version() == lb.ABI_VERSION and llib.cflb_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFLB_ABI_VERSION (\d+)", text).group(1)) == lb.ABI_VERSION
     assert int(re.search(r"#define CFLB_MAX_HEADS (\d+)", text).group(1)) == lb.MAX_HEADS == 16
     assert int(re.search(r"#define CFLB_FRAME_BATCH (\d+)", text).group(1)) == lb.FRAME_BATCH
     assert int(re.search(r"#define CFLB_TOKEN_CHUNK (\d+)", text).group(1)) == lb.TOKEN_CHUNK
@@ -46,77 +34,7 @@ def test_header_exported_exactly_and_arity_matches(llib):
 
 
 def test_abi_version_is_checked_at_load(llib, monkeypatch):
-    from clip_fsar_amd import lastblock_hip as lb
-    monkeypatch.setattr(lb, "_lib", None)
-    monkeypatch.setattr(lb, "ABI_VERSION", lb.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        lb.lib()
-    monkeypatch.setattr(lb, "LIB_PATH", lb.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        lb.lib()
-
-
-def test_the_other_eight_libraries_export_nothing_of_it(llib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, groups_hip, hip, ingest_hip, lastblock_hip, live_hip, pool_hip, stream_hip
-    ours = _exported(lastblock_hip.LIB_PATH)
-    assert ours and all(s.startswith("cflb_") for s in ours), sorted(ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip, groups_hip):
-        assert not any(s.startswith("cflb_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(llib):
-    from clip_fsar_amd import build as b
-    sl = b.TOWER_LIBS["lastblock"]
-    if not os.path.exists(sl.usage):
-        b.build_side("lastblock", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    # the two folds for bf16 and fp16 operands, class attend for up to 2, 12 and 16 heads
-    assert len(names) == 7 and [len([n for n in names if k in n]) for k in ("key_fold_kernel", "value_fold_kernel", "class_attend_kernel")] \
-        == [2, 2, 3], names
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "lastblock.hip" and sl.source not in b.SOURCES and sl.lib.endswith(os.sep + "libclipfsar_lastblock.so")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "lastblock", "resource_usage.json"))
-    others = [b.USAGE] + [b._side_lib(n).usage for n in SEVEN]
-    assert len(set(others)) == 8 and sl.usage not in others
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-
-
-def test_three_registries_disjoint_and_built_by_build(llib):
-    from clip_fsar_amd import build as b
-    assert list(b.TOWER_LIBS) == ["lastblock"] and b.tower_lib_names() == ["lastblock"]
-    assert b.every_side_lib_names() == SEVEN and b.side_lib_names() == SEVEN[:6]           # what the earlier checks enumerate
-    assert not set(b.TOWER_LIBS) & (set(b.SIDE_LIBS) | set(b.MORE_SIDE_LIBS))
-    assert b._side_lib("lastblock") is b.TOWER_LIBS["lastblock"]
-    with pytest.raises(KeyError):
-        b._side_lib("nobody")
-    # the fixture ran build(): every library of the three registries is there
-    for name in SEVEN + ["lastblock"]:
-        assert os.path.exists(b._side_lib(name).lib), name
-    assert os.path.exists(b.LIB)
-
-
-def test_an_edited_file_makes_exactly_the_libraries_that_reach_it_stale(monkeypatch):
-    from clip_fsar_amd import build as b
-    names = SEVEN + ["lastblock"]
-    stale_by_file = {
-        "lastblock.hip": {"lastblock"},
-        "clipfsar_lastblock.h": {"lastblock"},
-        "groups.hip": {"groups"},
-        "side_lib.h": set(names),
-        "common.h": set(names) | {"product"},
-        "tail.hip": {"product"},
-    }
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    for edited, want in sorted(stale_by_file.items()):
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + edited) else 1.0)
-        stale = {"product"} if b._stale(b.LIB, b._product_deps()) else set()
-        stale |= {n for n in names if b._stale(b._side_lib(n).lib, b._side_deps(n))}
-        assert stale == want, edited
-    assert os.path.join(b.CSRC, "lastblock.hip") not in b._product_deps()
+    check_abi_at_load(lib_row("lastblock"), monkeypatch)
 
 
 # ------------------------------------------------------------------ argument validation, without a GPU

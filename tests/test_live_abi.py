@@ -1,8 +1,7 @@
-"""CPU: the live-gallery library (libclipfsar_live.so, include/clipfsar_live.h) builds beside the other six libraries, exports exactly its
-header, validates arguments and descriptor tables without a GPU, keeps its kernels out of scratch, and is stale exactly when its own files
-or the headers it shares change; LiveGallery's slot and column bookkeeping (the plan_* functions) against a model on random schedules."""
+"""CPU: the live-gallery library (libclipfsar_live.so, include/clipfsar_live.h) validates arguments and descriptor tables without a GPU;
+LiveGallery's slot and column bookkeeping (the plan_* functions) against a model on random schedules.  Its exports, kernels and place in the
+build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -10,7 +9,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _other_reports, _prototypes
+from _abi import check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_live.h")
@@ -19,25 +18,15 @@ HEADER = os.path.join(ROOT, "include", "clipfsar_live.h")
 @pytest.fixture(scope="module")
 def llib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all seven libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import live_hip
     return live_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(llib):
+    check_exports(lib_row("live"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import live_hip as lh
-    protos = _prototypes(HEADER, "cfsl_")
-    assert set(protos) == {"cfsl_version", "cfsl_abi_version", "cfsl_last_error", "cfsl_otam_indexed", "cfsl_accumulate",
-                           "cfsl_slot_norms"}, protos
-    assert _exported(lh.LIB_PATH) == set(protos), sorted(_exported(lh.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfsl_last_error":
-            continue
-        assert len(lh.SIGNATURES[name]) == nargs, (name, len(lh.SIGNATURES[name]), nargs)
-    assert set(lh.SIGNATURES) | {"cfsl_last_error"} == set(protos)
-    assert llib.cfsl_abi_version() == lh.ABI_VERSION and llib.cfsl_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFSL_ABI_VERSION (\d+)", text).group(1)) == lh.ABI_VERSION
     assert int(re.search(r"#define CFSL_MAX_T (\d+)", text).group(1)) == lh.MAX_T == 32
     assert int(re.search(r"#define CFSL_MAX_ROWS (\d+)", text).group(1)) == lh.MAX_ROWS
     assert int(re.search(r"#define CFSL_TABLE_COLS (\d+)", text).group(1)) == lh.TABLE_COLS == 4
@@ -46,43 +35,7 @@ def test_header_exported_exactly_and_arity_matches(llib):
 
 
 def test_abi_version_is_checked_at_load(llib, monkeypatch):
-    from clip_fsar_amd import live_hip as lh
-    monkeypatch.setattr(lh, "_lib", None)
-    monkeypatch.setattr(lh, "ABI_VERSION", lh.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        lh.lib()
-    monkeypatch.setattr(lh, "LIB_PATH", lh.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        lh.lib()
-
-
-def test_the_other_six_libraries_export_nothing_of_it(llib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, ingest_hip, live_hip, pool_hip, stream_hip
-    ours = _exported(live_hip.LIB_PATH)
-    assert ours and all(s.startswith("cfsl_") for s in ours), sorted(ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip):
-        assert not any(s.startswith("cfsl_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(llib):
-    from clip_fsar_amd import build as b
-    sl = b.SIDE_LIBS["live"]
-    if not os.path.exists(sl.usage):
-        b.build_side("live", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    assert len(names) == 5 and len([n for n in names if "otam_indexed_kernel" in n]) == 3, names      # T = 8, T = 16, run-time T
-    assert any("accumulate_kernel" in n for n in names) and any("slot_norms_kernel" in n for n in names)
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source not in b.SOURCES
-    others = _other_reports("live")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "live", "resource_usage.json"))
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-    patterns = set(open(os.path.join(ROOT, ".gitignore")).read().split())
-    assert {"*.so", "*.o", "build/"} <= patterns and sl.lib.endswith(os.sep + "libclipfsar_live.so")
+    check_abi_at_load(lib_row("live"), monkeypatch)
 
 
 # ------------------------------------------------------------------ validation, without a GPU

@@ -1,9 +1,7 @@
-"""CPU: the grouped text library (libclipfsar_live_text.so, include/clipfsar_live_text.h) builds beside the other ten as one more name of
-the fourth registry, exports exactly its header, checks its ABI revision at load, validates its descriptor table without a GPU, keeps its
-kernels out of scratch and is stale exactly when its own files or the headers it reaches change; the softmax code it shares with
-gallery_text.hip has one copy; plan_text_groups against a list model; misuse of LiveTextGallery on a stub head; the state dicts."""
+"""CPU: the grouped text library (libclipfsar_live_text.so, include/clipfsar_live_text.h) validates its descriptor table without a GPU;
+plan_text_groups against a list model; misuse of LiveTextGallery on a stub head; the state dicts.  Its exports, kernels and place in the
+build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -11,37 +9,27 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _prototypes
+from _abi import _prototypes, check_abi_at_load, check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_live_text.h")
-TEN = ["gallery", "gallery_text", "stream", "pool", "ingest", "live", "groups", "lastblock", "enroll"]      # + the product library
 
 
 @pytest.fixture(scope="module")
 def tlib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all eleven libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import live_text_hip
     return live_text_hip.lib()
 
 
-# ------------------------------------------------------------------ the library and its place in the build
+# ------------------------------------------------------------------ what is particular to this library's header and source
 def test_header_exported_exactly_and_arity_matches(tlib):
+    check_exports(lib_row("live_text"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import live_text_hip as lt
     protos = _prototypes(HEADER, "cflt_")
-    assert set(protos) == {"cflt_version", "cflt_abi_version", "cflt_last_error", "cflt_workspace_floats", "cflt_text_logits_grouped",
-                           "cflt_text_softmax_grouped", "cflt_text_combine_grouped"}, protos
-    assert _exported(lt.LIB_PATH) == set(protos), sorted(_exported(lt.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cflt_last_error":
-            continue
-        assert len(lt.SIGNATURES[name]) == nargs, (name, len(lt.SIGNATURES[name]), nargs)
-    assert set(lt.SIGNATURES) | {"cflt_last_error"} == set(protos)
     assert protos["cflt_text_logits_grouped"] == 18
-    assert tlib.cflt_abi_version() == lt.ABI_VERSION and tlib.cflt_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFLT_ABI_VERSION (\d+)", text).group(1)) == lt.ABI_VERSION
     assert int(re.search(r"#define CFLT_TABLE_COLS (\d+)", text).group(1)) == lt.TABLE_COLS == 8
     assert int(re.search(r"#define CFLT_MAX_GROUPS (\d+)", text).group(1)) == lt.MAX_GROUPS
     for i, col in enumerate(("Q0", "NQ", "C0", "NC", "TILE0", "OUT0", "PART0", "PAD")):       # the binding's column order is the header's
@@ -50,91 +38,14 @@ def test_header_exported_exactly_and_arity_matches(tlib):
 
 
 def test_abi_version_is_checked_at_load(tlib, monkeypatch):
-    from clip_fsar_amd import live_text_hip as lt
-    monkeypatch.setattr(lt, "_lib", None)
-    monkeypatch.setattr(lt, "ABI_VERSION", lt.ABI_VERSION + 1)
-    with pytest.raises(RuntimeError, match="ABI revision"):
-        lt.lib()
-    monkeypatch.setattr(lt, "LIB_PATH", lt.LIB_PATH + ".absent")
-    with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
-        lt.lib()
+    check_abi_at_load(lib_row("live_text"), monkeypatch)
 
 
-def test_the_other_ten_libraries_export_nothing_of_it(tlib):
-    from clip_fsar_amd import (enroll_hip, gallery_hip, gallery_text_hip, groups_hip, hip, ingest_hip, lastblock_hip, live_hip,
-                               live_text_hip, pool_hip, stream_hip)
-    ours = _exported(live_text_hip.LIB_PATH)
-    assert ours and all(s.startswith("cflt_") for s in ours), sorted(ours)
-    for mod in (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip, groups_hip, lastblock_hip, enroll_hip):
-        assert not any(s.startswith("cflt_") for s in _exported(mod.LIB_PATH)), mod.__name__
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(tlib):
+def test_the_source_allocates_nothing_and_holds_no_matrix_code_of_its_own():
     from clip_fsar_amd import build as b
-    sl = b._side_lib("live_text")
-    assert sl is b.LATER_SIDE_LIBS["live_text"] and list(b.LATER_SIDE_LIBS) == ["enroll", "live_text"]
-    assert b._all_lib_names() == TEN + ["live_text"]
-    if not os.path.exists(sl.usage):
-        b.build_side("live_text", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    assert len(usage) == 3, sorted(usage)
-    for k in ("text_logits_grouped_kernel", "text_softmax_grouped_kernel", "text_combine_grouped_kernel"):
-        assert sum(k in n for n in usage) == 1, (k, sorted(usage))
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "live_text.hip" and sl.source not in b.SOURCES and sl.lib.endswith(os.sep + "libclipfsar_live_text.so")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "live_text", "resource_usage.json"))
-    others = [b.USAGE] + [b._side_lib(n).usage for n in TEN]
-    assert len(set(others)) == 10 and sl.usage not in others
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-    src = open(os.path.join(b.CSRC, sl.source)).read()
+    src = open(os.path.join(b.CSRC, b.SIDE_LIBS["live_text"].source)).read()
     for body in ("asm", "__builtin_amdgcn_mfma", "thread_local", "hipMalloc", "hipStreamCreate"):
         assert body not in src, body
-
-
-def test_an_edited_file_makes_exactly_the_libraries_that_reach_it_stale(monkeypatch):
-    from clip_fsar_amd import build as b
-    names = b._all_lib_names()
-    stale_by_file = {
-        "live_text.hip": {"live_text"},
-        "clipfsar_live_text.h": {"live_text"},
-        "text_softmax.h": {"gallery_text", "live_text"},
-        "fp32_tile_gemm.h": {"gallery", "gallery_text", "live", "groups", "live_text"},
-        "side_lib.h": set(names),
-        "common.h": set(names) | {"product"},
-        "gallery_text.hip": {"gallery_text"},
-        "groups.hip": {"groups"},
-        "tail.hip": {"product"},
-    }
-    monkeypatch.setattr(b.os.path, "exists", lambda p: True)
-    for edited, want in sorted(stale_by_file.items()):
-        monkeypatch.setattr(b.os.path, "getmtime", lambda p: 2.0 if p.endswith(os.sep + edited) else 1.0)
-        stale = {"product"} if b._stale(b.LIB, b._product_deps()) else set()
-        stale |= {n for n in names if b._stale(b._side_lib(n).lib, b._side_deps(n))}
-        assert stale == want, edited
-    deps = b._product_deps()
-    for f in ("live_text.hip", "text_softmax.h"):
-        assert os.path.join(b.CSRC, f) not in deps, f
-
-
-def test_the_softmax_code_has_one_copy():
-    from clip_fsar_amd import build as b
-    src = lambda name: open(os.path.join(b.CSRC, name)).read()
-    shared, dense, grouped = src("text_softmax.h"), src("gallery_text.hip"), src("live_text.hip")
-    for body in ("void merge_partials(", "void row_pass4(", "float block_max(", "float block_sum(", "void text_tile_epilogue(",
-                 "void text_softmax_row(", "void text_combine_row("):
-        assert shared.count(body) == 1, body
-        assert body not in dense and body not in grouped, body
-    for text in (dense, grouped):
-        assert '#include "text_softmax.h"' in text
-        assert text.count("text_tile_epilogue(") == 1 and text.count("text_softmax_row(") == 1 and text.count("text_combine_row(") == 1
-        for body in ("powf(", "wave_max(", "wave_sum(", "fmaxf(", "merge_partials(", "__builtin_amdgcn_mfma"):
-            assert body not in text, body
-    assert src("fp32_tile_gemm.h").count("__builtin_amdgcn_mfma_f32_16x16x4f32") == 1
-    assert "fp32_tile_gemm(" in dense and grouped.count("fp32_tile_gemm_rows(") == 1 and "LookedUpRow{" in grouped
-    assert "store_slot_row(" in grouped and "store_slot_norm(" in grouped and "cols[c0" not in grouped     # the slot arithmetic: otam_tile.h
 
 
 # ------------------------------------------------------------------ table validation, without a GPU

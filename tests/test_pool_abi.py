@@ -1,8 +1,7 @@
-"""CPU: the stream-pool library (libclipfsar_pool.so, include/clipfsar_pool.h) builds beside the other four libraries, exports exactly its
-header, validates arguments and descriptor tables without a GPU, keeps its kernels out of scratch; the host plan of a push (plan_push, slot
-assignment) against a brute-force model of the ring over random schedules; StreamPool's constructor and session errors on a stub head."""
+"""CPU: the stream-pool library (libclipfsar_pool.so, include/clipfsar_pool.h) validates arguments and descriptor tables without a GPU; the
+host plan of a push (plan_push, slot assignment) against a brute-force model of the ring over random schedules; StreamPool's constructor and
+session errors on a stub head.  Its exports, kernels and place in the build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -10,7 +9,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _other_reports, _prototypes
+from _abi import check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_pool.h")
@@ -19,47 +18,21 @@ HEADER = os.path.join(ROOT, "include", "clipfsar_pool.h")
 @pytest.fixture(scope="module")
 def plib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all five libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import pool_hip
     return pool_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(plib):
+    check_exports(lib_row("pool"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import pool_hip as ph
-    protos = _prototypes(HEADER, "cfsp_")
-    assert set(protos) == {"cfsp_version", "cfsp_abi_version", "cfsp_last_error", "cfsp_ring_put", "cfsp_window_sequences",
-                           "cfsp_smooth_logits"}, protos
-    assert _exported(ph.LIB_PATH) == set(protos), sorted(_exported(ph.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfsp_last_error":
-            continue
-        assert len(ph.SIGNATURES[name]) == nargs, (name, len(ph.SIGNATURES[name]), nargs)
-    assert set(ph.SIGNATURES) | {"cfsp_last_error"} == set(protos)
-    assert plib.cfsp_abi_version() == ph.ABI_VERSION and plib.cfsp_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFSP_ABI_VERSION (\d+)", text).group(1)) == ph.ABI_VERSION
     assert int(re.search(r"#define CFSP_MAX_T (\d+)", text).group(1)) == ph.MAX_T == 32
     assert int(re.search(r"#define CFSP_MAX_STREAMS (\d+)", text).group(1)) == ph.MAX_STREAMS
     assert int(re.search(r"#define CFSP_TABLE_COLS (\d+)", text).group(1)) == ph.TABLE_COLS == 8
     cols = ("SLOT", "PUT_POS", "N", "FEAT_OFF", "WIN_POS", "NW", "WIN_OFF", "HAS_STATE")
     for i, col in enumerate(cols):                # the binding's column order is the header's
         assert int(re.search(r"#define CFSP_%s (\d+)" % col, text).group(1)) == getattr(ph, col) == i
-
-
-def test_other_libraries_keep_their_export_sets(plib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, pool_hip, stream_hip
-    ours = _exported(pool_hip.LIB_PATH)
-    assert not any(s.startswith(("cfsg_", "cfsar_", "cfgt_", "cfss_")) for s in ours)
-    want = {hip: ("cfsar_", "clipfsar_hip.h", 48), gallery_hip: ("cfsg_", "clipfsar_gallery.h", 8),
-            gallery_text_hip: ("cfgt_", "clipfsar_gallery_text.h", 8), stream_hip: ("cfss_", "clipfsar_stream.h", 6)}
-    for mod, (prefix, header, count) in want.items():
-        protos = _prototypes(os.path.join(ROOT, "include", header), prefix)
-        assert len(protos) == count, (header, len(protos))
-        syms = _exported(mod.LIB_PATH)
-        assert not any(s.startswith("cfsp_") for s in syms), mod.__name__
-        if mod is hip and os.environ.get("CFSAR_DEV", "0") == "1":
-            continue                              # a developer build of the product library exports its debug hooks too
-        assert syms == set(protos), (mod.__name__, sorted(syms ^ set(protos)))
 
 
 # ------------------------------------------------------------------ validation, without a GPU
@@ -170,35 +143,6 @@ def test_python_wrappers_reject_cpu_tensors_and_bad_tables(plib):
         ph.TableUploader("cpu", 4).upload([[0] * 8] * 5)
     with pytest.raises(RuntimeError, match="1 .. 4 rows"):
         ph.TableUploader("cpu", 4).upload([])
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(plib):
-    from clip_fsar_amd import build as b
-    sl = b.SIDE_LIBS["pool"]
-    if not os.path.exists(sl.usage):
-        b.build_side("pool", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    for k, count in (("pool_ring_put_kernel", 2), ("pool_window_sequences_kernel", 2), ("pool_smooth_logits_kernel", 1)):
-        assert sum(k in n for n in names) == count, (k, names)                     # 16-byte and 4-byte forms
-    assert len(names) == 5, names
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "pool.hip" and sl.source not in b.SOURCES
-    others = _other_reports("pool")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "pool", "resource_usage.json"))
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
-
-
-def test_build_products_are_git_ignored():
-    """libclipfsar_pool.so and build/pool/ fall under the patterns that keep the other libraries' products out of git"""
-    from clip_fsar_amd import build as b
-    patterns = set(open(os.path.join(ROOT, ".gitignore")).read().split())
-    assert {"*.so", "*.o", "build/"} <= patterns
-    sl = b.SIDE_LIBS["pool"]
-    assert sl.lib.endswith(".so") and os.sep + "build" + os.sep in sl.usage
 
 
 # ------------------------------------------------------------------ the host plan against a model of the ring

@@ -1,8 +1,7 @@
-"""CPU: the window-stream library (libclipfsar_stream.so, include/clipfsar_stream.h) builds beside the other three libraries, exports
-exactly its header, validates arguments without a GPU, keeps its kernels out of scratch; window_plan emits every window once, in order, with
-the push that delivers its last frame; WindowStream's constructor errors on a stub head."""
+"""CPU: the window-stream library (libclipfsar_stream.so, include/clipfsar_stream.h) validates arguments without a GPU; window_plan emits every
+window once, in order, with the push that delivers its last frame; WindowStream's constructor errors on a stub head.  Its exports, kernels
+and place in the build are checked with every library's in tests/test_build_recipe.py."""
 import ctypes
-import json
 import os
 import random
 import re
@@ -10,7 +9,7 @@ from types import SimpleNamespace as NS
 
 import pytest
 
-from _abi import _exported, _other_reports, _prototypes
+from _abi import check_exports, lib_row
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "clipfsar_stream.h")
@@ -20,42 +19,16 @@ I64 = ctypes.c_int64
 @pytest.fixture(scope="module")
 def slib():
     import __graft_entry__ as ge
-    ge.build()                                    # builds all four libraries (no-op when up to date)
+    ge.build()                                    # builds every library (no-op when up to date)
     from clip_fsar_amd import stream_hip
     return stream_hip.lib()
 
 
 def test_header_exported_exactly_and_arity_matches(slib):
+    check_exports(lib_row("stream"))                 # the checks every library gets; below, what is particular to this one
     from clip_fsar_amd import stream_hip as sh
-    protos = _prototypes(HEADER, "cfss_")
-    assert set(protos) == {"cfss_version", "cfss_abi_version", "cfss_last_error", "cfss_ring_put", "cfss_window_sequences",
-                           "cfss_smooth_logits"}, protos
-    assert _exported(sh.LIB_PATH) == set(protos), sorted(_exported(sh.LIB_PATH) ^ set(protos))
-    for name, nargs in protos.items():
-        if name == "cfss_last_error":
-            continue
-        assert len(sh.SIGNATURES[name]) == nargs, (name, len(sh.SIGNATURES[name]), nargs)
-    assert set(sh.SIGNATURES) | {"cfss_last_error"} == set(protos)
-    assert slib.cfss_abi_version() == sh.ABI_VERSION and slib.cfss_version() >= 100
     text = open(HEADER).read()
-    assert int(re.search(r"#define CFSS_ABI_VERSION (\d+)", text).group(1)) == sh.ABI_VERSION
     assert int(re.search(r"#define CFSS_MAX_T (\d+)", text).group(1)) == sh.MAX_T == 32
-
-
-def test_other_libraries_keep_their_export_sets(slib):
-    from clip_fsar_amd import gallery_hip, gallery_text_hip, hip, stream_hip
-    ours = _exported(stream_hip.LIB_PATH)
-    assert not any(s.startswith(("cfsg_", "cfsar_", "cfgt_")) for s in ours)
-    want = {hip: ("cfsar_", "clipfsar_hip.h", 48), gallery_hip: ("cfsg_", "clipfsar_gallery.h", 8),
-            gallery_text_hip: ("cfgt_", "clipfsar_gallery_text.h", 8)}
-    for mod, (prefix, header, count) in want.items():
-        protos = _prototypes(os.path.join(ROOT, "include", header), prefix)
-        assert len(protos) == count, (header, len(protos))
-        syms = _exported(mod.LIB_PATH)
-        assert not any(s.startswith("cfss_") for s in syms), mod.__name__
-        if mod is hip and os.environ.get("CFSAR_DEV", "0") == "1":
-            continue                              # a developer build of the product library exports its debug hooks too
-        assert syms == set(protos), (mod.__name__, sorted(syms ^ set(protos)))
 
 
 def test_argument_validation_without_gpu(slib):
@@ -113,26 +86,6 @@ def test_python_wrappers_reject_cpu_tensors(slib):
         sh.window_sequences(torch.zeros(2, 9, 8), torch.zeros(3, 4, 8), 2, 4, 1, 1, 0, 5)
     with pytest.raises(RuntimeError, match="shape"):
         sh.smooth_logits(torch.zeros(2, 3, 5), torch.zeros(2, 4), torch.zeros(2, 3, 5), 0.5, 0)
-
-
-def test_kernels_use_no_scratch_and_stay_out_of_the_other_reports(slib):
-    from clip_fsar_amd import build as b
-    sl = b.SIDE_LIBS["stream"]
-    if not os.path.exists(sl.usage):
-        b.build_side("stream", force=True, verbose=False)
-    usage = json.load(open(sl.usage))
-    names = sorted(usage)
-    for k, count in (("ring_put_kernel", 2), ("window_sequences_kernel", 2), ("smooth_logits_kernel", 1)):    # 16-byte and 4-byte forms
-        assert sum(k in n for n in names) == count, (k, names)
-    assert len(names) == 5, names
-    for n, u in usage.items():
-        assert u.get("scratch", 0) == 0 and u.get("spills", 0) == 0, (n, u)
-    assert sl.source == "stream.hip" and sl.source not in b.SOURCES
-    others = _other_reports("stream")
-    assert os.path.normpath(sl.usage).endswith(os.path.join("build", "stream", "resource_usage.json"))
-    for other in others:
-        if os.path.exists(other):
-            assert not set(usage) & set(json.load(open(other))), other
 
 
 # ------------------------------------------------------------------ the host plan
