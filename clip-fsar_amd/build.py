@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so and the side libraries (SIDE_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so, the side libraries (SIDE_LIBS) and the extension libraries (EXT_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -35,14 +35,20 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
-# The side libraries, in the order they are built: the support gallery, its text half (EVAL_TEXT / COMBINE), the window streams' ring,
-# gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, the live gallery, grouped scoring, the last
-# ViT block's class-token attention without its K | V projection, enrolment out of the stream pool's ring, and the text branches over
+# Two tiers of libraries beside libclipfsar_hip.so.
+# SIDE_LIBS, the side libraries, in the order they are built: the support gallery, its text half (EVAL_TEXT / COMBINE), the window streams'
+# ring, gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, the live gallery, grouped scoring, the
+# last ViT block's class-token attention without its K | V projection, enrolment out of the stream pool's ring, and the text branches over
 # grouped slot lists; C ABI of each in include/clipfsar_<name>.h.  Each is ONE source, csrc/<name>.hip, compiled with the product FLAGS and
 # the fence into a library of its own beside libclipfsar_hip.so (the pinned export sets stay apart), stale when a file its source reaches
-# through #include is newer, with its own resource report (build/resource_usage.json stays the product library's).  This dict is the only
-# registry (when a library is loaded is its binding's business, not the build's): a further library is one more name here, and one more
-# row in the table of tests/_abi.py.
+# through #include is newer, with its own resource report (build/resource_usage.json stays the product library's).  This tier is CLOSED:
+# the table of tests/_abi.py and the staleness matrix of tests/test_build_recipe.py pin its ten names, every file of csrc/ and every
+# include/clipfsar_*.h, so nothing is added to it and csrc/ takes no new file.
+# EXT_LIBS (below build_side), the extension libraries, built after the side libraries by the same recipe -- one source, the same flags
+# and fence, the same staleness rule, a resource report of its own -- from ext/<name>.hip with the C ABI in include/ext/clipfsar_<name>.h.
+# A further library goes there: one more name in EXT_LIBS, its binding, and a test_<name>_abi.py with a _abi.Lib row of its own.  An
+# extension's source may include csrc/ headers (the shared code keeps its one copy); nothing of csrc/ includes an extension.
+# When a library is loaded is its binding's business, not the build's.
 SideLib = collections.namedtuple("SideLib", "source lib usage")
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
                            os.path.join(HERE, "build", name, "resource_usage.json"))
@@ -111,7 +117,7 @@ PACKED_LIB = os.path.join(HERE, "libclipfsar_hip_packed.so")
 
 
 def _compile(src, obj, extra, verbose) -> dict:
-    """hipcc -c one source of csrc/ with FLAGS + extra; the resource-usage remarks come back parsed, the compiler's other output is printed"""
+    """hipcc -c one source (a name of csrc/, or an absolute path) with FLAGS + extra; the resource-usage remarks come back parsed, the compiler's other output is printed"""
     cmd = [HIPCC] + FLAGS + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
     if verbose:
         print(" ".join(cmd), flush=True)
@@ -147,12 +153,43 @@ def build_side(name, force: bool = False, verbose: bool = True) -> str:
     return _link(sl.lib, [obj], _compile(sl.source, obj, NO_PACKED_FP32, verbose), sl.usage, verbose)
 
 
+# The extension tier (the comment above SIDE_LIBS): per-class smoothing of the stream pool.  A namedtuple type of its own, so that the
+# side libraries' registry stays the only dict of SideLib values.
+ExtLib = collections.namedtuple("ExtLib", "source header lib usage")
+EXT = os.path.join(HERE, "ext")
+EXT_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
+                         os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
+            for name in ("class_smooth",)}
+
+
+def ext_lib_names() -> list:
+    return list(EXT_LIBS)
+
+
+def _ext_deps(name) -> list:
+    return sorted(_includes(EXT_LIBS[name].source)) + [os.path.abspath(__file__)]
+
+
+def build_ext(name, force: bool = False, verbose: bool = True) -> str:
+    """an extension library (a name of EXT_LIBS): build_side's recipe on ext/<name>.hip -- the product FLAGS, the packed-fp32 fence, stale
+    when a file the source reaches through #include (or this file) is newer, resource report -> .usage"""
+    el = EXT_LIBS[name]
+    if not force and not _stale(el.lib, _ext_deps(name)):
+        return el.lib
+    bdir = os.path.dirname(el.usage)
+    os.makedirs(bdir, exist_ok=True)
+    obj = os.path.join(bdir, name + ".o")
+    return _link(el.lib, [obj], _compile(el.source, obj, NO_PACKED_FP32, verbose), el.usage, verbose)
+
+
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
-    The product build also builds the side libraries (build_side)."""
+    The product build also builds the side libraries (build_side) and, after them, the extension libraries (build_ext)."""
     if not (dev or packed or variant):
         for name in side_lib_names():
             build_side(name, force=force, verbose=verbose)
+        for name in ext_lib_names():
+            build_ext(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):
         return LIB_OUT

@@ -16,6 +16,9 @@ in place, and between growths (1.5 x when full) the store's address does not mov
     r = g.classify_grouped(queries, counts=[3, 2], classes=[[9, 2], None])      # 3 clips against [9, 2], the next 2 against every class:
     r.group(0), r.group(1), r.logits             # [3, 2] and [2, C] views of the flat logits; one scoring launch (libclipfsar_groups.so)
     g.shots(9); g.state_dict()                   # SupportGallery's keys (dense, column order) + "sums" and "counts"
+    g.slot_of(9); g.slot_generations()           # a class's store slot, and every slot's generation ([capacity] int32 on the device): it rises
+                                                 # when a slot is freed or changes owner, so state kept per slot elsewhere (StreamPool's
+                                                 # per-class smoothing) knows whether it still belongs to the slot's class
 
 A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
 support sequences before context2) and its shot count: further shots continue the sum in cfsg_segment_mean's operation order
@@ -200,6 +203,7 @@ class LiveGallery(_GalleryBase):
         self._retired = []                                 # (outgrown store, the event behind the work queued on it)
         self._tables = self._group_tables = None
         self._book = self._active = None
+        self._slot_gen, self._slot_gen_dev = [], None      # the store slots' generations (_install keeps them) and their device copy
         self.clear()
 
     def _check_branch(self, cfg):
@@ -215,9 +219,24 @@ class LiveGallery(_GalleryBase):
         self._bind()
         version = 0 if self._book is None else self._book.version + bool(self._book.order)
         cap = self._store_cap() if self._store is not None else self._capacity
-        self._install(new_book(cap)._replace(version=version))
+        self._install(new_book(cap)._replace(version=version), renew=True)
 
-    def _install(self, book):
+    def _install(self, book, renew=False):
+        """the Book a call leaves behind.  The slots' generations follow it: a slot that was freed, or whose class is another one now, gets
+        the next generation (renew: every slot does -- clear() and load_state_dict, after which no slot holds what it held); the slots a
+        growth adds start at 1."""
+        old = self._book
+        gen = self._slot_gen
+        if renew or old is None:
+            changed = range(len(gen))
+        else:
+            owner = {s: c for c, s in book.slot_of.items()}
+            changed = [s for c, s in old.slot_of.items() if s not in owner or owner[s] != c]
+        for s in changed:
+            gen[s] += 1
+        gen.extend([1] * (book.cap - len(gen)))
+        if changed or self._slot_gen_dev is None or self._slot_gen_dev.shape[0] != len(gen):
+            self._slot_gen_dev = None                      # uploaded anew on demand: a launch in flight keeps the tensor it was given
         self._book = book
         self._ids = book.order                             # _GalleryBase: len(), class_ids, "no classes registered"
         self._cols = None                                  # device column list of all classes, made on demand
@@ -232,6 +251,17 @@ class LiveGallery(_GalleryBase):
     @property
     def capacity(self):
         return self._book.cap
+
+    def slot_generation(self, slot):
+        """the generation of a store slot: at least 1, and higher after every time the slot was freed or changed its owner"""
+        return self._slot_gen[slot]
+
+    def slot_generations(self):
+        """[capacity] int32 on the device: every store slot's generation.  Whoever keeps state per store slot (StreamPool's per-class
+        smoothing) stores the generation beside it, and the state is valid iff the two still agree."""
+        if self._slot_gen_dev is None:
+            self._slot_gen_dev = torch.tensor(self._slot_gen, device=self.dev, dtype=torch.int32)
+        return self._slot_gen_dev
 
     def shots(self, cid):
         """the shot count of a class (0: loaded from a SupportGallery state, whose sums are not known)"""
@@ -584,4 +614,4 @@ class LiveGallery(_GalleryBase):
             st["text"][:C].copy_(f32(text))
             if sums is not None:
                 st["sums"][:C].copy_(f32(sums))
-        self._install(book._replace(version=old_version + 1))
+        self._install(book._replace(version=old_version + 1), renew=True)

@@ -259,4 +259,4 @@ class LiveTextGallery(LiveGallery):
                 st["pn"][:C * T].copy_(f32(pn))
                 if sums is not None:
                     st["sums"][:C].copy_(f32(sums))
-        self._install(book._replace(version=old_version + 1))
+        self._install(book._replace(version=old_version + 1), renew=True)

@@ -10,7 +10,8 @@
     p.push_u8({a: ua, b: ub}); p.push_u8_packed([ua, ub], [a, b])     # decoded uint8 [n, H, W, 3] clips, each of its own H x W, on the host
                                                                       # or the device: clip_fsar_amd.ingest.FrameIngest, then push_packed
     values, index = p.topk(po, k=5)
-    c = p.open(classes=[9, 2])             # a session with columns of its own (a tenant's classes); needs a LiveGallery and smooth = 0
+    c = p.open(classes=[9, 2])             # a session with columns of its own (a tenant's classes); needs a LiveGallery, and smooth = 0
+                                           # unless the pool smooths by class (below)
     out = p.push({a: fa, c: fc})           # out[c].logits [nWc, 2], out[a].logits [nWa, C]: still one tower call sequence, and one grouped
                                            # scoring launch per chunk of windows; the *_packed forms then return a GroupedPackedOutput
     p.enroll(a, class_id=7)                # the session's newest complete window becomes a shot of class 7 (a new class, or a further
@@ -18,6 +19,8 @@
     p.enrolable(a)                         # range of the window numbers still in the ring; p.enroll(a, 7, window=w, join=True)
     p.enroll_windows([(a, None, 7), (b, 3, 7), (b, 4, "kite")], text={"kite": "flying a kite"})     # -> {7: 2, "kite": 1}
     p.reset(a); p.close(a); p.stats(a); p.stats()
+    q = StreamPool(live_gallery, smooth=0.5, smooth_by="class")      # smoothing state per (session, class) instead of per column: class
+    c = q.open(classes=[9, 2]); q.enroll(c, "kite", join=True)        # lists, enrolment and removals while sessions run, no reset()
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -29,6 +32,14 @@ A push is described to the device by one descriptor table with a row per session
 write per round, one gather plus one classify_features per chunk of windows, whatever the number of sessions.  A session's push beyond
 max_push frames is split into rounds (round r takes up to max_push of what each session has left).  Sessions absent from a push are
 untouched.  Smoothing state is per session: y_0 = x_0, y_k = fmaf(alpha, y_{k-1}, (1 - alpha) * x_k), the bits of WindowStream's.
+
+smooth_by="class" (a LiveGallery or LiveTextGallery): the state is [max_streams, store capacity], a cell per (session slot, class store
+slot), and beside every cell lies the generation the store slot had when the cell was written (LiveGallery.slot_generations).  A cell
+continues the recurrence iff that mark is the slot's current generation, so a pair starts anew (y = x) at its first window after the
+session's open() or reset() (the session's row of marks is zeroed), after the class's registration (the gallery bumps the generation of
+a slot that was freed or changed owner), and after the class joined the session's list -- and at nothing else: other classes coming and
+going, further shots, store growth and other sessions leave it alone.  One launch per push (libclipfsar_class_smooth.so,
+clip_fsar_amd.class_smooth_hip), once the push's logits are in session-major order; the bits are the column mode's where both apply.
 
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
@@ -42,6 +53,7 @@ import heapq
 
 import torch
 
+from . import class_smooth_hip as cship
 from . import enroll_hip as enhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
@@ -53,7 +65,9 @@ from .stream import StreamOutput, window_plan
 PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
 # Of a push in which a session has a class list of its own: logits is flat, session i owning [logit_offsets[i], logit_offsets[i + 1]) as
 # a row-major [offsets[i + 1] - offsets[i], widths[i]] block (windows ascending).
-GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions first_window offsets logits logit_offsets widths")
+# smoothed: of a pool with smooth_by="class", flat in the layout of logits; None otherwise.
+GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions first_window offsets logits logit_offsets widths smoothed",
+                                             defaults=(None,))
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
@@ -142,7 +156,7 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None):
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column"):
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -155,6 +169,15 @@ class StreamPool:
             raise ValueError("StreamPool: smooth must be in [0, 1), got %r" % smooth)
         if gallery.T > php.MAX_T:
             raise ValueError("StreamPool: T = %d frames per window, the pool library gathers at most %d" % (gallery.T, php.MAX_T))
+        if smooth_by not in ("column", "class"):
+            raise ValueError("StreamPool: smooth_by must be \"column\" or \"class\", got %r" % (smooth_by,))
+        if smooth_by == "class" and not hasattr(gallery, "slot_generations"):
+            raise ValueError("StreamPool: smooth_by=\"class\" needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
+                             % type(gallery).__name__)
+        if smooth_by == "class" and smooth and max_streams * gallery.capacity > cship.MAX_CELLS:
+            raise ValueError(self._too_many_cells(max_streams, gallery.capacity))
+        self.smooth_by = smooth_by
+        self._by_class = smooth_by == "class" and bool(smooth)     # with smooth = 0 the option is inert
         self.gallery = gallery
         self.dev = gallery.dev
         self.max_streams, self.stride, self.rate, self.max_push, self.alpha = max_streams, stride, rate, max_push, smooth
@@ -164,6 +187,10 @@ class StreamPool:
         self._X = None                           # gathered windows [rows, T, E], grown on demand
         self._state = None                       # smoothing state [max_streams, C], indexed by slot
         self._state_gen = 0                      # bumped whenever _state is allocated anew (the class count changed)
+        self._marks = None                       # smooth_by="class": _state is [max_streams, store capacity] by (slot, store slot), and
+        self._unmarked = set()                   # _marks the generations beside it; the slots whose row of marks is to be zeroed
+        self._smooth_tables = None               # class_smooth_hip's descriptor tables, made by the first class-mode push
+        self._smooth_keys = (None, None, None)   # the last push's own store-slot lists, the gallery's column list then, their device form
         self._tables = php.TableUploader(self.dev, max_streams)
         self._enroll_tables = None               # enrolment lists (enroll_hip's row layout), made by the first enroll
         self._sessions = {}                      # handle -> _Session
@@ -185,7 +212,7 @@ class StreamPool:
             if not hasattr(self.gallery, "classify_features_grouped"):
                 raise ValueError("StreamPool: open(classes=) needs a gallery that scores groups (a LiveGallery), not a %s"
                                  % type(self.gallery).__name__)
-            if self.alpha:
+            if self.alpha and not self._by_class:
                 raise ValueError("StreamPool: open(classes=) on a pool with smooth > 0 is not supported -- smoothing with per-session "
                                  "class lists is out of scope; build the pool with smooth = 0")
             self._session_lists([self._next_handle], [classes])
@@ -195,6 +222,8 @@ class StreamPool:
         h = self._next_handle
         self._next_handle += 1
         self._sessions[h] = _Session(heapq.heappop(self._free), classes)
+        if self._by_class:
+            self._unmarked.add(self._sessions[h].slot)      # nothing of the slot's previous owner is read
         return h
 
     def _session_lists(self, handles, lists):
@@ -217,7 +246,10 @@ class StreamPool:
 
     def reset(self, h):
         """Frame counter 0; the session's ring contents and smoothing state are dropped."""
-        self._session(h).clear()
+        s = self._session(h)
+        s.clear()
+        if self._by_class:
+            self._unmarked.add(s.slot)
 
     @property
     def sessions(self):
@@ -264,7 +296,7 @@ class StreamPool:
 
     def _check_state(self, sessions, recs):
         self._session_lists(sessions, [s.classes for s in recs])         # a class removed since open(): raised here, before any launch
-        if self.alpha:
+        if self.alpha and not self._by_class:
             C = len(self.gallery)
             fresh = self._state is None or self._state.shape[1] != C
             for h, s in zip(sessions, recs):
@@ -317,8 +349,8 @@ class StreamPool:
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
             if isinstance(po, GroupedPackedOutput):
-                block = po.logits[po.logit_offsets[i]:po.logit_offsets[i + 1]]
-                out[h] = StreamOutput(po.first_window[i], block.view(w1 - w0, po.widths[i]), None)
+                block = lambda t: t[po.logit_offsets[i]:po.logit_offsets[i + 1]].view(w1 - w0, po.widths[i])
+                out[h] = StreamOutput(po.first_window[i], block(po.logits), None if po.smoothed is None else block(po.smoothed))
                 continue
             out[h] = StreamOutput(po.first_window[i], po.logits[w0:w1], None if po.smoothed is None else po.smoothed[w0:w1])
         return out
@@ -416,17 +448,67 @@ class StreamPool:
             s.t += n
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += offsets[-1]
-        return GroupedPackedOutput(handles, plan.first_window, offsets, logits, logit_offsets, widths)
+        smoothed = self._smooth_classes(recs, plan.n_windows, logits) if self._by_class else None
+        return GroupedPackedOutput(handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
+
+    @staticmethod
+    def _too_many_cells(max_streams, cap):
+        return ("StreamPool: smooth_by=\"class\" keeps a state cell per (session slot, store slot): max_streams = %d x store capacity = %d "
+                "is 2^31 or more -- build the pool with fewer streams or the gallery with fewer slots" % (max_streams, cap))
+
+    def _class_state(self, cap):
+        """state and marks [max_streams, cap]; a grown store: reallocated with their columns copied, the marks' new columns invalid.  The
+        rows of marks of sessions opened or reset since the last push are zeroed here, on the push's stream."""
+        if self.max_streams * cap > cship.MAX_CELLS:
+            raise ValueError(self._too_many_cells(self.max_streams, cap))
+        old = None if self._state is None else self._state.shape[1]
+        if old != cap:
+            state = torch.empty(self.max_streams, cap, device=self.dev, dtype=torch.float32)
+            marks = torch.zeros(self.max_streams, cap, device=self.dev, dtype=torch.int32)
+            if old is not None:
+                state[:, :old].copy_(self._state)
+                marks[:, :old].copy_(self._marks)
+            self._state, self._marks = state, marks
+        for slot in sorted(self._unmarked):
+            self._marks[slot].zero_()
+        self._unmarked.clear()
+        return self._state, self._marks
+
+    def _smooth_classes(self, recs, n_windows, logits):
+        """smooth_by="class": the push's logits, session-major (dense [NW, C] or the grouped layout), -> their smoothed values in the same
+        layout; one launch over every session of the push"""
+        smoothed = torch.empty_like(logits)
+        if not logits.numel():
+            return smoothed
+        g = self.gallery
+        book = g._book
+        plan = cship.plan_rows([s.slot for s in recs], n_windows, [None if s.classes is None else [book.slot_of[c] for c in s.classes]
+                                                                   for s in recs], len(book.order))
+        gens = g.slot_generations()
+        state, marks = self._class_state(gens.shape[0])
+        # the device keys: the gallery's own column list (every class's store slot, cached there until the classes change) for the sessions
+        # without a list, the own lists behind it -- a push without lists uploads nothing
+        every = g._columns(None) if plan.every else None
+        key = tuple(plan.keys)
+        if self._smooth_keys[0] != key or self._smooth_keys[1] is not every:
+            own = torch.tensor(plan.keys, device=self.dev, dtype=torch.int32) if key else None
+            self._smooth_keys = (key, every, own if every is None else every if own is None else torch.cat([every, own]))
+        if self._smooth_tables is None:
+            self._smooth_tables = cship.table_uploader(self.dev, self.max_streams)
+        cship.smooth_classes(logits.view(-1), state, marks, gens, self._smooth_keys[2], smoothed.view(-1),
+                             self._smooth_tables.upload(plan.rows), self.alpha)
+        return smoothed
 
     def _run(self, eng, feats, handles, recs, counts):
         if any(s.classes is not None for s in recs):
             return self._run_grouped(eng, feats, handles, recs, counts)
         g, T, C = self.gallery, self.T, len(self.gallery)
-        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push, smoothing=bool(self.alpha))
+        by_column = bool(self.alpha) and not self._by_class
+        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push, smoothing=by_column)
         NW = sum(plan.n_windows)
         logits = torch.empty(NW, C, device=self.dev, dtype=torch.float32)
-        smoothed = torch.empty_like(logits) if self.alpha else None
-        if self.alpha and NW and (self._state is None or self._state.shape[1] != C):
+        smoothed = torch.empty_like(logits) if by_column else None
+        if by_column and NW and (self._state is None or self._state.shape[1] != C):
             self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
             self._state_gen += 1
         g0 = 0
@@ -434,17 +516,19 @@ class StreamPool:
             out = logits[g0:g0 + nW]
             out[w0:w1].copy_(g.classify_features(X))
             if w1 == nW:                         # the round's last chunk
-                if self.alpha:
+                if by_column:
                     php.smooth_logits(out, self._state, smoothed[g0:g0 + nW], table, self.alpha)
                 g0 += nW
         if plan.order is not None and NW:        # several rounds: round-major -> session-major
             index = torch.tensor(plan.order, device=self.dev)
             logits = logits.index_select(0, index)
-            smoothed = smoothed.index_select(0, index) if self.alpha else None
+            smoothed = smoothed.index_select(0, index) if by_column else None
+        if self._by_class:                       # one launch, on the session-major logits: a session's rounds stay in sequence
+            smoothed = self._smooth_classes(recs, plan.n_windows, logits)
         offsets = [0]
         for s, n, nW in zip(recs, counts, plan.n_windows):
             s.t += n
-            if self.alpha and nW:
+            if by_column and nW:
                 s.state_gen = self._state_gen
                 s.state_layout = getattr(g, "layout_version", None)
             offsets.append(offsets[-1] + nW)
@@ -537,7 +621,7 @@ class StreamPool:
 
     # ------------------------------------------------------------------ top-k
     def _topk_grouped(self, out, k, smoothed):
-        if smoothed:
+        if smoothed and out.smoothed is None:
             raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")
         n_windows = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])]
         widths = [C for nW, C in zip(n_windows, out.widths) if nW]
@@ -546,7 +630,7 @@ class StreamPool:
         if not out.offsets[-1]:
             return (torch.empty(0, k, device=self.dev, dtype=torch.float32), torch.empty(0, k, device=self.dev, dtype=torch.int32))
         rows, _ = grhip.table_rows(n_windows, out.widths, self.T)
-        return self.gallery.topk_of_groups(out.logits, rows, k)
+        return self.gallery.topk_of_groups(out.smoothed if smoothed else out.logits, rows, k)
 
     def topk(self, out, k=5, smoothed=False):
         """(values [nW, k] fp32 descending, class index [nW, k] int32 into gallery.class_ids) of every window of a PackedOutput or a
