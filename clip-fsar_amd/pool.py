@@ -21,6 +21,9 @@
     p.reset(a); p.close(a); p.stats(a); p.stats()
     q = StreamPool(live_gallery, smooth=0.5, smooth_by="class")      # smoothing state per (session, class) instead of per column: class
     c = q.open(classes=[9, 2]); q.enroll(c, "kite", join=True)        # lists, enrolment and removals while sessions run, no reset()
+    r = StreamPool(live_gallery, smooth=0.5, smooth_by="class", events=EventRule(on=0.6, off=0.4, min_on=2, min_off=2))
+    r.push_features({a: fa}); r.take_events()                         # [Event(session, class_id, kind, window, start, length, score, peak)]
+    r.active(a)                                                       # [(class_id, length, peak)] of the session's running events
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -41,6 +44,17 @@ a slot that was freed or changed owner), and after the class joined the session'
 going, further shots, store growth and other sessions leave it alone.  One launch per push (libclipfsar_class_smooth.so,
 clip_fsar_amd.class_smooth_hip), once the push's logits are in session-major order; the bits are the column mode's where both apply.
 
+events=EventRule(...) (clip_fsar_amd.events; a LiveGallery or LiveTextGallery): every push that completes a window also runs a hysteresis
+detector over each (session, class) pair's scores -- the smoothed ones when the pool smooths by class, the logits or probabilities
+otherwise -- on the device (libclipfsar_events.so, clip_fsar_amd.events_hip: one call per push, on the session-major scores, over the
+descriptor table and key lists of the class mode, which are then planned and uploaded once for both).  Its state is the pool's own, keyed
+and guarded like the class mode's, so events run through class lists, enrolment, join=True, removals and slot reuse; a removed class and a
+closed or reset session end their events silently.  The push returns what it returns without a rule and does not synchronise: it queues
+the device's records with the metadata fixed at push time, and take_events() synchronises once and returns the Events push by push,
+within a push in session order as pushed, then window, then column.  The queue holds EVENT_QUEUE pushes; a push onto a full queue
+translates the oldest batch itself (one synchronisation) and keeps its events for the next take_events().  Records beyond the rule's
+max_events per push are dropped with a RuntimeWarning and counted in stats()["events_dropped"].
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -50,14 +64,17 @@ from __future__ import annotations
 
 import collections
 import heapq
+import warnings
 
 import torch
 
 from . import class_smooth_hip as cship
 from . import enroll_hip as enhip
+from . import events_hip as evhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
+from .events import EventRule, translate
 from .gallery import _GalleryBase
 from .ingest import FrameIngest
 from .stream import StreamOutput, window_plan
@@ -72,6 +89,10 @@ GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions fi
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
 Plan = collections.namedtuple("Plan", "rounds first_window n_windows order")
+# What a push with an event rule queues: buf, the device's int32 answer (n_events, then the events and values of events_hip.detect), and
+# the metadata fixed at push time, per table row: the session's handle, its first window of the push and its columns' class ids.
+EventBatch = collections.namedtuple("EventBatch", "buf sessions first_window class_ids")
+EVENT_QUEUE = 64                                  # pushes whose records may wait for take_events()
 
 
 def plan_push(sessions, counts, T, stride, rate, max_push, smoothing=False):
@@ -156,7 +177,7 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column"):
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column", events=None):
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -176,6 +197,17 @@ class StreamPool:
                              % type(gallery).__name__)
         if smooth_by == "class" and smooth and max_streams * gallery.capacity > cship.MAX_CELLS:
             raise ValueError(self._too_many_cells(max_streams, gallery.capacity))
+        if events is not None:
+            if not isinstance(events, EventRule):
+                raise TypeError("StreamPool: events must be an EventRule, got %s" % type(events).__name__)
+            if not hasattr(gallery, "slot_generations"):
+                raise ValueError("StreamPool: events= needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
+                                 % type(gallery).__name__)
+            if smooth and smooth_by == "column":
+                raise ValueError("StreamPool: events= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
+                                 "keyed by column, the detector's by class")
+            if max_streams * gallery.capacity > evhip.MAX_CELLS:
+                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "events="))
         self.smooth_by = smooth_by
         self._by_class = smooth_by == "class" and bool(smooth)     # with smooth = 0 the option is inert
         self.gallery = gallery
@@ -197,6 +229,15 @@ class StreamPool:
         self._free = list(range(max_streams))    # a heap: the lowest free slot is taken first
         self._next_handle = 0
         self._totals = {"frames": 0, "tower_frames": 0, "windows": 0}
+        self._events = events                    # the EventRule, or None: nothing below is there
+        if events is not None:
+            self._totals.update(events=0, events_dropped=0)
+            self._ev_cells = None                # (streak, length, peak, marks), each [max_streams, store capacity]
+            self._ev_unmarked = set()            # the slots whose row of the detector's marks is to be zeroed, as _unmarked
+            self._ev_work = None                 # events_hip.detect's workspace, grown on demand
+            self._ev_queue = collections.deque() # EventBatch per push that ran the detector, oldest first
+            self._ev_ready = []                  # Events of batches a push had to translate itself
+            self._ev_ids = (None, None)          # (layout_version, class count) and the gallery's class ids then
         if ingest is not None and not isinstance(ingest, FrameIngest):
             raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
         if ingest is not None:
@@ -224,6 +265,8 @@ class StreamPool:
         self._sessions[h] = _Session(heapq.heappop(self._free), classes)
         if self._by_class:
             self._unmarked.add(self._sessions[h].slot)      # nothing of the slot's previous owner is read
+        if self._events is not None:
+            self._ev_unmarked.add(self._sessions[h].slot)
         return h
 
     def _session_lists(self, handles, lists):
@@ -250,13 +293,16 @@ class StreamPool:
         s.clear()
         if self._by_class:
             self._unmarked.add(s.slot)
+        if self._events is not None:
+            self._ev_unmarked.add(s.slot)
 
     @property
     def sessions(self):
         return sorted(self._sessions)
 
     def stats(self, h=None):
-        """of a session: frames, tower_frames and windows since open() / reset(); of the pool: what all pushes added up to, and the open sessions"""
+        """of a session: frames, tower_frames and windows since open() / reset(); of the pool: what all pushes added up to, and the open
+        sessions -- with an event rule also "events" and "events_dropped", the records translated so far and those beyond max_events"""
         if h is None:
             return dict(self._totals, open=len(self._sessions))
         s = self._session(h)
@@ -448,13 +494,16 @@ class StreamPool:
             s.t += n
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += offsets[-1]
-        smoothed = self._smooth_classes(recs, plan.n_windows, logits) if self._by_class else None
+        cp = self._class_push(recs, plan.n_windows) if (self._by_class or self._events is not None) and logits.numel() else None
+        smoothed = self._smooth_classes(cp, logits) if self._by_class else None
+        if cp is not None and self._events is not None:
+            self._detect(handles, recs, plan, smoothed if self._by_class else logits, cp)
         return GroupedPackedOutput(handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
 
     @staticmethod
-    def _too_many_cells(max_streams, cap):
-        return ("StreamPool: smooth_by=\"class\" keeps a state cell per (session slot, store slot): max_streams = %d x store capacity = %d "
-                "is 2^31 or more -- build the pool with fewer streams or the gallery with fewer slots" % (max_streams, cap))
+    def _too_many_cells(max_streams, cap, what="smooth_by=\"class\""):
+        return ("StreamPool: %s keeps a state cell per (session slot, store slot): max_streams = %d x store capacity = %d "
+                "is 2^31 or more -- build the pool with fewer streams or the gallery with fewer slots" % (what, max_streams, cap))
 
     def _class_state(self, cap):
         """state and marks [max_streams, cap]; a grown store: reallocated with their columns copied, the marks' new columns invalid.  The
@@ -474,18 +523,14 @@ class StreamPool:
         self._unmarked.clear()
         return self._state, self._marks
 
-    def _smooth_classes(self, recs, n_windows, logits):
-        """smooth_by="class": the push's logits, session-major (dense [NW, C] or the grouped layout), -> their smoothed values in the same
-        layout; one launch over every session of the push"""
-        smoothed = torch.empty_like(logits)
-        if not logits.numel():
-            return smoothed
+    def _class_push(self, recs, n_windows):
+        """what the launches over (session slot, store slot) cells share in one push -- per-class smoothing and the event detector: the
+        host plan, the store slots' generations, the device keys and the uploaded descriptor table"""
         g = self.gallery
         book = g._book
         plan = cship.plan_rows([s.slot for s in recs], n_windows, [None if s.classes is None else [book.slot_of[c] for c in s.classes]
                                                                    for s in recs], len(book.order))
         gens = g.slot_generations()
-        state, marks = self._class_state(gens.shape[0])
         # the device keys: the gallery's own column list (every class's store slot, cached there until the classes change) for the sessions
         # without a list, the own lists behind it -- a push without lists uploads nothing
         every = g._columns(None) if plan.every else None
@@ -495,9 +540,127 @@ class StreamPool:
             self._smooth_keys = (key, every, own if every is None else every if own is None else torch.cat([every, own]))
         if self._smooth_tables is None:
             self._smooth_tables = cship.table_uploader(self.dev, self.max_streams)
-        cship.smooth_classes(logits.view(-1), state, marks, gens, self._smooth_keys[2], smoothed.view(-1),
-                             self._smooth_tables.upload(plan.rows), self.alpha)
+        return plan, gens, self._smooth_keys[2], self._smooth_tables.upload(plan.rows)
+
+    def _smooth_classes(self, cp, logits):
+        """smooth_by="class": the push's logits, session-major (dense [NW, C] or the grouped layout), -> their smoothed values in the same
+        layout; one launch over every session of the push.  cp: _class_push's, None when the push completed no window"""
+        smoothed = torch.empty_like(logits)
+        if cp is None:
+            return smoothed
+        _, gens, keys, table = cp
+        state, marks = self._class_state(gens.shape[0])
+        cship.smooth_classes(logits.view(-1), state, marks, gens, keys, smoothed.view(-1), table, self.alpha)
         return smoothed
+
+    # ------------------------------------------------------------------ events
+    def _event_cells(self, cap):
+        """the detector's cells (streak, length, peak, marks), each [max_streams, cap], grown with the store as _class_state grows its
+        own: the columns copied, the marks' new columns invalid; the rows of marks of sessions opened or reset since the last push are
+        zeroed here, on the push's stream"""
+        if self.max_streams * cap > evhip.MAX_CELLS:
+            raise ValueError(self._too_many_cells(self.max_streams, cap, "events="))
+        old = None if self._ev_cells is None else self._ev_cells[0].shape[1]
+        if old != cap:
+            new = tuple((torch.zeros if i == 3 else torch.empty)(self.max_streams, cap, device=self.dev,
+                                                                 dtype=torch.float32 if i == 2 else torch.int32) for i in range(4))
+            if old is not None:
+                for t, was in zip(new, self._ev_cells):
+                    t[:, :old].copy_(was)
+            self._ev_cells = new
+        for slot in sorted(self._ev_unmarked):
+            self._ev_cells[3][slot].zero_()
+        self._ev_unmarked.clear()
+        return self._ev_cells
+
+    def _every_class_ids(self):
+        g = self.gallery
+        key = (g.layout_version, len(g))          # columns change their meaning with a removal and are appended by an addition
+        if self._ev_ids[0] != key:
+            self._ev_ids = (key, tuple(g.class_ids))
+        return self._ev_ids[1]
+
+    def _detect(self, handles, recs, plan, scores, cp):
+        """one cfev_detect over the push's session-major scores (three launches, no synchronisation); the records stay on the device and
+        are queued with the push's metadata"""
+        rule = self._events
+        cplan, gens, keys, table = cp
+        cells = self._event_cells(gens.shape[0])
+        need = evhip.workspace_ints(cplan.n_chunks)
+        if self._ev_work is None or self._ev_work.shape[0] < need:
+            self._ev_work = torch.empty(need, device=self.dev, dtype=torch.int32)
+        M = rule.max_events
+        buf = torch.empty(1 + (evhip.EVENT_COLS + evhip.VALUE_COLS) * M, device=self.dev, dtype=torch.int32)
+        events, values = self._records(buf, M)
+        evhip.detect(scores.view(-1), *cells, gens, keys, events, values, buf[:1], self._ev_work, table, rule.on, rule.off, rule.min_on,
+                     rule.min_off)
+        if len(self._ev_queue) >= EVENT_QUEUE:     # a full queue: the oldest batch is translated here and kept for take_events()
+            self._ev_ready.extend(self._translate([self._ev_queue.popleft()]))
+        every = None
+        ids = []
+        for s in recs:
+            if s.classes is None:
+                every = self._every_class_ids() if every is None else every
+            ids.append(every if s.classes is None else s.classes)       # a session's list is replaced (enroll's join), never changed
+        self._ev_queue.append(EventBatch(buf, handles, plan.first_window, ids))
+
+    @staticmethod
+    def _records(buf, M):
+        """the events [M, 5] int32 and values [M, 2] fp32 inside an EventBatch's buffer (buf[0] is n_events)"""
+        split = 1 + evhip.EVENT_COLS * M
+        return buf[1:split].view(M, evhip.EVENT_COLS), buf[split:].view(torch.float32).view(M, evhip.VALUE_COLS)
+
+    def _translate(self, batches):
+        """EventBatches -> their Events, batch by batch; one synchronising copy"""
+        if not batches:
+            return []
+        M = self._events.max_events
+        host = (batches[0].buf[None] if len(batches) == 1 else torch.stack([b.buf for b in batches])).cpu()
+        out, dropped = [], 0
+        for b, h in zip(batches, host):
+            n = int(h[0])
+            kept = min(n, M)
+            events, values = self._records(h, M)
+            out.extend(translate(events[:kept], values[:kept], kept, b.sessions, b.first_window, b.class_ids, self._events))
+            self._totals["events"] += kept
+            dropped += n - kept
+        if dropped:
+            self._totals["events_dropped"] += dropped
+            warnings.warn("StreamPool: %d event records beyond max_events = %d per push were dropped (the detector's state advanced all "
+                          "the same) -- build the rule with a larger max_events" % (dropped, M), RuntimeWarning, stacklevel=3)
+        return out
+
+    def _need_rule(self, what):
+        if self._events is None:
+            raise ValueError("StreamPool.%s: this pool has no event rule (build it with events=EventRule(...))" % what)
+
+    def take_events(self):
+        """the Events of every push since the last call, push by push; within a push in session order as pushed, then window, then
+        column.  Synchronises once; clears the queue."""
+        self._need_rule("take_events")
+        batches = list(self._ev_queue)
+        self._ev_queue.clear()
+        out, self._ev_ready = self._ev_ready, []
+        out.extend(self._translate(batches))
+        return out
+
+    def active(self, h):
+        """[(class_id, length, peak)]: the session's pairs whose event is running -- active cells whose mark is the store slot's current
+        generation -- in the order of the session's columns.  Synchronises."""
+        self._need_rule("active")
+        s = self._session(h)
+        if self._ev_cells is None or s.slot in self._ev_unmarked:
+            return []
+        streak, length, peak, marks = self._ev_cells
+        book = self.gallery._book
+        ids = [c for c in (book.order if s.classes is None else s.classes) if c in book.slot_of and book.slot_of[c] < marks.shape[1]]
+        if not ids:
+            return []
+        at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
+        gens = self.gallery.slot_generations().index_select(0, at)
+        on = ((marks[s.slot].index_select(0, at) == gens) & (streak[s.slot].index_select(0, at) < 0)).tolist()
+        lens, peaks = length[s.slot].index_select(0, at).tolist(), peak[s.slot].index_select(0, at).tolist()
+        return [(c, n, p) for c, live, n, p in zip(ids, on, lens, peaks) if live]
 
     def _run(self, eng, feats, handles, recs, counts):
         if any(s.classes is not None for s in recs):
@@ -523,8 +686,11 @@ class StreamPool:
             index = torch.tensor(plan.order, device=self.dev)
             logits = logits.index_select(0, index)
             smoothed = smoothed.index_select(0, index) if by_column else None
+        cp = self._class_push(recs, plan.n_windows) if (self._by_class or self._events is not None) and NW else None
         if self._by_class:                       # one launch, on the session-major logits: a session's rounds stay in sequence
-            smoothed = self._smooth_classes(recs, plan.n_windows, logits)
+            smoothed = self._smooth_classes(cp, logits)
+        if cp is not None and self._events is not None:
+            self._detect(handles, recs, plan, smoothed if self._by_class else logits, cp)
         offsets = [0]
         for s, n, nW in zip(recs, counts, plan.n_windows):
             s.t += n
