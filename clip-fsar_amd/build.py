@@ -1,4 +1,4 @@
-"""Build libclipfsar_hip.so, the side libraries (SIDE_LIBS), the extension libraries (EXT_LIBS) and the add-on libraries (ADDON_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libclipfsar_hip.so, the side libraries (SIDE_LIBS), the extension libraries (EXT_LIBS), the add-on libraries (ADDON_LIBS) and the plug-in libraries (PLUGIN_LIBS) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python clip-fsar_amd/build.py [--force]
 
@@ -35,7 +35,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hi
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {src: NO_PACKED_FP32 for src in SOURCES}
 USAGE = os.path.join(HERE, "build", "resource_usage.json")
-# Two tiers of libraries beside libclipfsar_hip.so.
+# Four tiers of libraries beside libclipfsar_hip.so; the first three are closed, the last one, PLUGIN_LIBS, is open.
 # SIDE_LIBS, the side libraries, in the order they are built: the support gallery, its text half (EVAL_TEXT / COMBINE), the window streams'
 # ring, gather and smoothing kernels, the same over the stream pool's descriptor table, frame ingest, the live gallery, grouped scoring, the
 # last ViT block's class-token attention without its K | V projection, enrolment out of the stream pool's ring, and the text branches over
@@ -49,8 +49,13 @@ USAGE = os.path.join(HERE, "build", "resource_usage.json")
 # This tier is closed as well: tests/test_class_smooth_abi.py pins its one name and the count of twelve libraries over both registries,
 # so a further library cannot be a second name of EXT_LIBS.  It goes into ADDON_LIBS (below build_ext), the add-on libraries, built after
 # the extensions by the same recipe again from ext/<name>.hip and include/ext/clipfsar_<name>.h: one more name there, its binding, and a
-# test_<name>_abi.py with a _abi.Lib row of its own.  An extension's or add-on's source may include csrc/ headers (the shared code keeps
-# its one copy); nothing of csrc/ includes one of them.
+# test_<name>_abi.py with a _abi.Lib row of its own.  That tier closed in its turn: tests/test_events_abi.py pins its one name and the
+# count of thirteen libraries over the three registries.  PLUGIN_LIBS (below build_addon), the plug-in libraries, built after the add-ons
+# by the same recipe once more, is the LAST registry and stays OPEN: a further library is one more name there, ext/<name>.hip,
+# include/ext/clipfsar_<name>.h, its binding and a test_<name>_abi.py with a _abi.Lib row of its own -- and such a test asserts that its
+# name is in the registry and follows the recipe, never the registry's length or a total count of libraries.  An extension's, add-on's
+# or plug-in's source may include csrc/ headers and headers of ext/ (the shared code keeps its one copy); nothing of csrc/ includes one
+# of them.
 # When a library is loaded is its binding's business, not the build's.
 SideLib = collections.namedtuple("SideLib", "source lib usage")
 SIDE_LIBS = {name: SideLib(name + ".hip", os.path.join(HERE, "libclipfsar_%s.so" % name),
@@ -208,10 +213,29 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
     return _build_ext_lib(name, ADDON_LIBS[name], _addon_deps(name), force, verbose)
 
 
+# The plug-in tier (the comment above SIDE_LIBS): adaptive baselines of the stream pool.  ExtLib values again; the open registry.
+PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
+                            os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
+               for name in ("baseline",)}
+
+
+def plugin_lib_names() -> list:
+    return list(PLUGIN_LIBS)
+
+
+def _plugin_deps(name) -> list:
+    return sorted(_includes(PLUGIN_LIBS[name].source)) + [os.path.abspath(__file__)]
+
+
+def build_plugin(name, force: bool = False, verbose: bool = True) -> str:
+    """a plug-in library (a name of PLUGIN_LIBS): build_ext's recipe, after the add-ons"""
+    return _build_ext_lib(name, PLUGIN_LIBS[name], _plugin_deps(name), force, verbose)
+
+
 def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: bool = False, variant: str = "", defs=()) -> str:
     """variant / defs (developer A/B): the product build with extra -D flags as libclipfsar_hip_<variant>.so (loaded through CFSAR_LIB_PATH).
-    The product build also builds the side libraries (build_side), after them the extension libraries (build_ext) and then the add-on
-    libraries (build_addon)."""
+    The product build also builds the side libraries (build_side), after them the extension libraries (build_ext), then the add-on
+    libraries (build_addon) and last the plug-in libraries (build_plugin)."""
     if not (dev or packed or variant):
         for name in side_lib_names():
             build_side(name, force=force, verbose=verbose)
@@ -219,6 +243,8 @@ def build(force: bool = False, verbose: bool = True, dev: bool = False, packed: 
             build_ext(name, force=force, verbose=verbose)
         for name in addon_lib_names():
             build_addon(name, force=force, verbose=verbose)
+        for name in plugin_lib_names():
+            build_plugin(name, force=force, verbose=verbose)
     LIB_OUT = os.path.join(HERE, "libclipfsar_hip_%s.so" % variant) if variant else (PACKED_LIB if packed else (DEV_LIB if dev else LIB))
     if not force and not _stale(LIB_OUT, _product_deps()):
         return LIB_OUT

@@ -24,6 +24,9 @@
     r = StreamPool(live_gallery, smooth=0.5, smooth_by="class", events=EventRule(on=0.6, off=0.4, min_on=2, min_off=2))
     r.push_features({a: fa}); r.take_events()                         # [Event(session, class_id, kind, window, start, length, score, peak)]
     r.active(a)                                                       # [(class_id, length, peak)] of the session's running events
+    z = StreamPool(live_gallery, baseline=Baseline(rate=1 / 32, warmup=16, gate=3.0), events=EventRule(on=4, off=2, min_on=2, min_off=2))
+    z.push_features({a: fa})[a].deviation                             # [nW, C]: (score - the pair's mean) / its deviation; the rule judges it
+    z.baseline(a)                                                     # [(class_id, mean, dev, n)] of the session's baselines
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -55,6 +58,15 @@ within a push in session order as pushed, then window, then column.  The queue h
 translates the oldest batch itself (one synchronisation) and keeps its events for the next take_events().  Records beyond the rule's
 max_events per push are dropped with a RuntimeWarning and counted in stats()["events_dropped"].
 
+baseline=Baseline(...) (clip_fsar_amd.baseline; a LiveGallery or LiveTextGallery): every push that completes a window also runs one
+launch (libclipfsar_baseline.so, clip_fsar_amd.baseline_hip) over the same session-major scores a rule would judge, after smoothing and
+before the detector, over the same table, keys and generations: each (session, class) pair keeps a running mean and mean absolute
+deviation of its own scores in cells keyed and guarded like the class mode's, and the push's output carries `deviation`, z = (score -
+mean) / deviation in the layout of logits, NaN through the pair's warm-up.  The outputs are then instances of subclasses of PackedOutput,
+GroupedPackedOutput and StreamOutput with the same tuple contents and that one attribute more.  With events= as well the detector judges
+z: the rule's thresholds are in units of the pair's own deviation and an Event's score and peak are deviations.  baseline(h) lists a
+session's cells.
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -68,12 +80,14 @@ import warnings
 
 import torch
 
+from . import baseline_hip as blhip
 from . import class_smooth_hip as cship
 from . import enroll_hip as enhip
 from . import events_hip as evhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
+from .baseline import Baseline
 from .events import EventRule, translate
 from .gallery import _GalleryBase
 from .ingest import FrameIngest
@@ -85,6 +99,23 @@ PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window off
 # smoothed: of a pool with smooth_by="class", flat in the layout of logits; None otherwise.
 GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions first_window offsets logits logit_offsets widths smoothed",
                                              defaults=(None,))
+
+
+def _with_deviation(base):
+    """the output type of a pool with a baseline: `base`'s tuple, and the attribute `deviation` beside it"""
+    class _Deviating(base):
+        def __new__(cls, *fields, deviation):
+            self = super().__new__(cls, *fields)
+            self.deviation = deviation
+            return self
+    _Deviating.__name__ = _Deviating.__qualname__ = "Deviation" + base.__name__
+    _Deviating.__doc__ = "%s of a pool with a baseline: the same tuple, and .deviation in the layout of .logits (NaN through warm-up)" % base.__name__
+    return _Deviating
+
+
+DeviationPackedOutput = _with_deviation(PackedOutput)
+DeviationGroupedPackedOutput = _with_deviation(GroupedPackedOutput)
+DeviationStreamOutput = _with_deviation(StreamOutput)
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
@@ -177,7 +208,8 @@ class _Session:
 
 
 class StreamPool:
-    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column", events=None):
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column", events=None,
+                 baseline=None):
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -208,6 +240,17 @@ class StreamPool:
                                  "keyed by column, the detector's by class")
             if max_streams * gallery.capacity > evhip.MAX_CELLS:
                 raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "events="))
+        if baseline is not None:
+            if not isinstance(baseline, Baseline):
+                raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
+            if not hasattr(gallery, "slot_generations"):
+                raise ValueError("StreamPool: baseline= needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
+                                 % type(gallery).__name__)
+            if smooth and smooth_by == "column":
+                raise ValueError("StreamPool: baseline= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
+                                 "keyed by column, the baseline's by class")
+            if max_streams * gallery.capacity > blhip.MAX_CELLS:
+                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "baseline="))
         self.smooth_by = smooth_by
         self._by_class = smooth_by == "class" and bool(smooth)     # with smooth = 0 the option is inert
         self.gallery = gallery
@@ -238,6 +281,10 @@ class StreamPool:
             self._ev_queue = collections.deque() # EventBatch per push that ran the detector, oldest first
             self._ev_ready = []                  # Events of batches a push had to translate itself
             self._ev_ids = (None, None)          # (layout_version, class count) and the gallery's class ids then
+        self._baseline = baseline                # the Baseline, or None: nothing below is there
+        if baseline is not None:
+            self._bl_cells = None                # (mean, dev, count, marks), each [max_streams, store capacity]
+            self._bl_unmarked = set()            # the slots whose row of the baselines' marks is to be zeroed, as _unmarked
         if ingest is not None and not isinstance(ingest, FrameIngest):
             raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
         if ingest is not None:
@@ -267,6 +314,8 @@ class StreamPool:
             self._unmarked.add(self._sessions[h].slot)      # nothing of the slot's previous owner is read
         if self._events is not None:
             self._ev_unmarked.add(self._sessions[h].slot)
+        if self._baseline is not None:
+            self._bl_unmarked.add(self._sessions[h].slot)
         return h
 
     def _session_lists(self, handles, lists):
@@ -295,6 +344,8 @@ class StreamPool:
             self._unmarked.add(s.slot)
         if self._events is not None:
             self._ev_unmarked.add(s.slot)
+        if self._baseline is not None:
+            self._bl_unmarked.add(s.slot)
 
     @property
     def sessions(self):
@@ -392,13 +443,15 @@ class StreamPool:
     def _split(po):
         """PackedOutput or GroupedPackedOutput -> {session: StreamOutput}"""
         out = {}
+        deviation = getattr(po, "deviation", None)      # of a pool with a baseline: each session's StreamOutput carries its block too
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
             if isinstance(po, GroupedPackedOutput):
                 block = lambda t: t[po.logit_offsets[i]:po.logit_offsets[i + 1]].view(w1 - w0, po.widths[i])
-                out[h] = StreamOutput(po.first_window[i], block(po.logits), None if po.smoothed is None else block(po.smoothed))
-                continue
-            out[h] = StreamOutput(po.first_window[i], po.logits[w0:w1], None if po.smoothed is None else po.smoothed[w0:w1])
+            else:
+                block = lambda t: t[w0:w1]
+            fields = (po.first_window[i], block(po.logits), None if po.smoothed is None else block(po.smoothed))
+            out[h] = StreamOutput(*fields) if deviation is None else DeviationStreamOutput(*fields, deviation=block(deviation))
         return out
 
     def push(self, frames):
@@ -494,11 +547,15 @@ class StreamPool:
             s.t += n
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += offsets[-1]
-        cp = self._class_push(recs, plan.n_windows) if (self._by_class or self._events is not None) and logits.numel() else None
+        cp = self._class_push(recs, plan.n_windows) if self._keyed and logits.numel() else None
         smoothed = self._smooth_classes(cp, logits) if self._by_class else None
+        judged = smoothed if self._by_class else logits
+        if self._baseline is not None:
+            judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, smoothed if self._by_class else logits, cp)
-        return GroupedPackedOutput(handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
+            self._detect(handles, recs, plan, judged, cp)
+        fields = (handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
+        return GroupedPackedOutput(*fields) if self._baseline is None else DeviationGroupedPackedOutput(*fields, deviation=deviation)
 
     @staticmethod
     def _too_many_cells(max_streams, cap, what="smooth_by=\"class\""):
@@ -552,6 +609,62 @@ class StreamPool:
         state, marks = self._class_state(gens.shape[0])
         cship.smooth_classes(logits.view(-1), state, marks, gens, keys, smoothed.view(-1), table, self.alpha)
         return smoothed
+
+    # ------------------------------------------------------------------ baselines
+    @property
+    def _keyed(self):
+        """whether a push runs a launch over (session slot, store slot) cells, i.e. needs _class_push's plan and upload"""
+        return self._by_class or self._events is not None or self._baseline is not None
+
+    def _baseline_cells(self, cap):
+        """the baselines' cells (mean, dev, count, marks), each [max_streams, cap], grown with the store as _class_state grows its own:
+        the columns copied, the marks' new columns invalid; the rows of marks of sessions opened or reset since the last push are zeroed
+        here, on the push's stream"""
+        if self.max_streams * cap > blhip.MAX_CELLS:
+            raise ValueError(self._too_many_cells(self.max_streams, cap, "baseline="))
+        old = None if self._bl_cells is None else self._bl_cells[0].shape[1]
+        if old != cap:
+            new = tuple((torch.zeros if i == 3 else torch.empty)(self.max_streams, cap, device=self.dev,
+                                                                 dtype=torch.float32 if i < 2 else torch.int32) for i in range(4))
+            if old is not None:
+                for t, was in zip(new, self._bl_cells):
+                    t[:, :old].copy_(was)
+            self._bl_cells = new
+        for slot in sorted(self._bl_unmarked):
+            self._bl_cells[3][slot].zero_()
+        self._bl_unmarked.clear()
+        return self._bl_cells
+
+    def _normalize(self, cp, scores):
+        """the push's session-major scores (dense [NW, C] or the grouped layout) -> their deviations in the same layout; one
+        cfbl_normalize over every session of the push.  cp: _class_push's, None when the push completed no window"""
+        deviation = torch.empty_like(scores)
+        if cp is None:
+            return deviation
+        b = self._baseline
+        _, gens, keys, table = cp
+        cells = self._baseline_cells(gens.shape[0])
+        blhip.normalize(scores.view(-1), *cells, gens, keys, deviation.view(-1), table, b.rate, b.warm_rate, b.warmup, b.gate, b.floor)
+        return deviation
+
+    def baseline(self, h):
+        """[(class_id, mean, dev, n)]: the session's baselines -- its cells whose mark is the store slot's current generation -- in the
+        order of the session's columns.  Synchronises."""
+        if self._baseline is None:
+            raise ValueError("StreamPool.baseline: this pool keeps no baselines (build it with baseline=Baseline(...))")
+        s = self._session(h)
+        if self._bl_cells is None or s.slot in self._bl_unmarked:
+            return []
+        mean, dev, count, marks = self._bl_cells
+        book = self.gallery._book
+        ids = [c for c in (book.order if s.classes is None else s.classes) if c in book.slot_of and book.slot_of[c] < marks.shape[1]]
+        if not ids:
+            return []
+        at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
+        gens = self.gallery.slot_generations().index_select(0, at)
+        valid = (marks[s.slot].index_select(0, at) == gens).tolist()
+        cols = [t[s.slot].index_select(0, at).tolist() for t in (mean, dev, count)]
+        return [(c, m, d, n) for c, live, m, d, n in zip(ids, valid, *cols) if live]
 
     # ------------------------------------------------------------------ events
     def _event_cells(self, cap):
@@ -686,11 +799,14 @@ class StreamPool:
             index = torch.tensor(plan.order, device=self.dev)
             logits = logits.index_select(0, index)
             smoothed = smoothed.index_select(0, index) if by_column else None
-        cp = self._class_push(recs, plan.n_windows) if (self._by_class or self._events is not None) and NW else None
+        cp = self._class_push(recs, plan.n_windows) if self._keyed and NW else None
         if self._by_class:                       # one launch, on the session-major logits: a session's rounds stay in sequence
             smoothed = self._smooth_classes(cp, logits)
+        judged = smoothed if self._by_class else logits
+        if self._baseline is not None:           # likewise one launch per push, after smoothing and before the detector
+            judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, smoothed if self._by_class else logits, cp)
+            self._detect(handles, recs, plan, judged, cp)
         offsets = [0]
         for s, n, nW in zip(recs, counts, plan.n_windows):
             s.t += n
@@ -700,7 +816,8 @@ class StreamPool:
             offsets.append(offsets[-1] + nW)
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += NW
-        return PackedOutput(handles, plan.first_window, offsets, logits, smoothed)
+        fields = (handles, plan.first_window, offsets, logits, smoothed)
+        return PackedOutput(*fields) if self._baseline is None else DeviationPackedOutput(*fields, deviation=deviation)
 
     # ------------------------------------------------------------------ enrolment
     def _enrolling_gallery(self):
