@@ -1,7 +1,7 @@
 """What the ctypes bindings (hip, gallery_hip, gallery_text_hip, stream_hip, pool_hip, ingest_hip, live_hip, groups_hip, lastblock_hip, enroll_hip, live_text_hip and
-the extension tier's class_smooth_hip, the add-on tier's events_hip and the plug-in tier's baseline_hip) share: loading a C-ABI
-library against its signature table, the builders of their ``_check`` / ``_shape`` helpers, and the descriptor table that six of them
-pass (class_smooth_hip, events_hip and baseline_hip too).  Each binding keeps its own SIGNATURES, ABI_VERSION, LIB_PATH and ``lib()``."""
+the extension tier's class_smooth_hip, the add-on tier's events_hip and the plug-in tier's baseline_hip and shortlist_hip) share: loading a
+C-ABI library against its signature table, the builders of their ``_check`` / ``_shape`` helpers, and the descriptor table that seven of
+them pass (class_smooth_hip, events_hip, baseline_hip and shortlist_hip too).  Each binding keeps its own SIGNATURES, ABI_VERSION, LIB_PATH and ``lib()``."""
 from __future__ import annotations
 
 import collections

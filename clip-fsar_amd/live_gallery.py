@@ -19,6 +19,8 @@ in place, and between growths (1.5 x when full) the store's address does not mov
     g.slot_of(9); g.slot_generations()           # a class's store slot, and every slot's generation ([capacity] int32 on the device): it rises
                                                  # when a slot is freed or changes owner, so state kept per slot elsewhere (StreamPool's
                                                  # per-class smoothing) knows whether it still belongs to the slot's class
+    g.slot_revision(slot)                        # host only: rises whenever the slot's prototype rows are written, further shots included, so what
+                                                 # is derived from a prototype (clip_fsar_amd.shortlist.Shortlist's coarse rows) knows when to follow
 
 A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
 support sequences before context2) and its shot count: further shots continue the sum in cfsg_segment_mean's operation order
@@ -204,6 +206,8 @@ class LiveGallery(_GalleryBase):
         self._tables = self._group_tables = None
         self._book = self._active = None
         self._slot_gen, self._slot_gen_dev = [], None      # the store slots' generations (_install keeps them) and their device copy
+        self._slot_rev = []                                # the store slots' revisions: host only (_install, _update_sequences)
+        self._writes = 0                                   # how often _touch_slots raised a revision: unchanged means no slot was written
         self.clear()
 
     def _check_branch(self, cfg):
@@ -235,6 +239,7 @@ class LiveGallery(_GalleryBase):
         for s in changed:
             gen[s] += 1
         gen.extend([1] * (book.cap - len(gen)))
+        self._touch_slots(range(len(self._slot_rev)) if renew else (), book.cap)
         if changed or self._slot_gen_dev is None or self._slot_gen_dev.shape[0] != len(gen):
             self._slot_gen_dev = None                      # uploaded anew on demand: a launch in flight keeps the tensor it was given
         self._book = book
@@ -262,6 +267,22 @@ class LiveGallery(_GalleryBase):
         if self._slot_gen_dev is None:
             self._slot_gen_dev = torch.tensor(self._slot_gen, device=self.dev, dtype=torch.int32)
         return self._slot_gen_dev
+
+    def slot_revision(self, slot):
+        """the revision of a store slot's prototype rows: it rises whenever they are written -- a registration, further shots (which leave
+        the generation alone), an enrolment, and for every slot clear() and load_state_dict; a growth copies the rows and keeps it.  Host
+        only.  Whoever keeps something derived from a slot's prototype (clip_fsar_amd.shortlist.Shortlist: its coarse rows) remembers the
+        revision it was computed at."""
+        return self._slot_rev[slot]
+
+    def _touch_slots(self, slots, cap=0):
+        """the revisions of `slots` rise; the list reaches at least cap slots (new ones start at 0)"""
+        rev = self._slot_rev
+        slots = list(slots)
+        rev.extend([0] * (max([cap] + [s + 1 for s in slots]) - len(rev)))
+        for s in slots:
+            rev[s] += 1
+        self._writes += bool(slots)
 
     def shots(self, cid):
         """the shot count of a class (0: loaded from a SupportGallery state, whose sums are not known)"""
@@ -312,6 +333,7 @@ class LiveGallery(_GalleryBase):
         n, prior)) into the store: sums, prototypes, norms.  SupportGallery's launch sequence after the support sequences -- context2 class
         by class -- with cfsl_accumulate in the place of cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone."""
         st, T, E, n = self._store, self.T, self.E, len(rows)
+        self._touch_slots([r[0] for r in rows])
         Y = None if self.merge_before else self._context2_by_class(eng, X0, offs)       # (:2955-2956)
         for c0 in range(0, n, TABLE_ROWS):
             c1 = min(n, c0 + TABLE_ROWS)
