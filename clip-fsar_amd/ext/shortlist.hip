@@ -2,20 +2,21 @@
 // (the mean of its unit-normalised rows), the coarse scores of every (query, class) pair as one exact-fp32 GEMM, and the selection that
 // turns them into per-group slot lists on the device, where cfgr_otam_grouped (groups.hip) reads them.  The pieces are the tree's where
 // they exist: the K loop is fp32_tile_gemm_rows with a looked-up B row (fp32_tile_gemm.h), the slot arithmetic is store_slot_row at one
-// row per class (otam_tile.h), as live_text.hip uses both.  What is new is select_kernel: a threshold select -- the K-th largest group
-// score by radix passes over order-preserving keys, then a scan that compacts the columns above the threshold and the first few equal to
-// it in ascending column order.  A record's place is a prefix sum, never the outcome of a race; the only atomics are the histogram
-// counts in LDS, whose sums do not depend on their order.
+// row per class (otam_tile.h), as live_text.hip uses both.  What is new is select_kernel (its body in select_keys.h): a threshold select
+// -- the K-th largest group score by radix passes over order-preserving keys, then a scan that compacts the columns above the threshold
+// and the first few equal to it in ascending column order.  A record's place is a prefix sum, never the outcome of a race; the only
+// atomics are the histogram counts in LDS, whose sums do not depend on their order.
 // A plug-in library (build.py, PLUGIN_LIBS): it lives beside csrc/, whose files and export sets stay as they are.
 #include "../csrc/otam_tile.h"
 #include "../../include/ext/clipfsar_shortlist.h"
+#include "select_keys.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int COLS = CFSH_TABLE_COLS;
-constexpr int WG = 256, WAVES = WG / 64;
+constexpr int WG = SEL_WG, WAVES = SEL_WAVES;
 constexpr long long MAX_32 = 0x7fffffffLL;
 
 // ---- the coarse row: one thread per float4 column of a sequence, sequential in t -- adjacent threads on adjacent columns, the norm a
@@ -73,125 +74,33 @@ __global__ __launch_bounds__(WG) void coarse_scores_kernel(const float* __restri
             }
 }
 
-// ---- the selection
-// a group score as a key that orders as the floats do: larger float, larger key; -0.0 folded into +0.0; 0 = not selectable (no score,
-// or -inf, whose key would be 0x007fffff: every selectable key is at least 0x00800000, that of -FLT_MAX)
-__device__ __forceinline__ unsigned score_key(float v, bool any) {
-    if (!any || !(v > -__builtin_inff())) return 0u;
-    const unsigned u = v == 0.0f ? 0u : __float_as_uint(v);                   // both zeros: the bits of +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// exclusive prefix of a flag over the workgroup's threads in thread order, and the workgroup's total: a ballot per wave, the waves'
-// counts through LDS.  Every thread calls it; `part` is WAVES ints, free to be rewritten after the call's second barrier.
-__device__ __forceinline__ unsigned block_prefix(bool flag, unsigned* part, unsigned& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) part[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const unsigned n = part[w];
-        before += w < wave ? n : 0u;
-        all += n;
-    }
-    __syncthreads();
-    total = all;
-    return before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-}
-
+// ---- the selection: the keys, the radix passes and the compaction are select_keys.h's, shared with pool_select.hip
 __global__ __launch_bounds__(WG) void select_kernel(const float* __restrict__ S, const int32_t* __restrict__ cols,
                                                     const int32_t* __restrict__ table, unsigned* __restrict__ work, int NQ, int NC, int K,
                                                     int32_t* __restrict__ sel_cols, int32_t* __restrict__ sel_slots) {
     __shared__ unsigned hist[WAVES * 256];                                    // a histogram per wave
     __shared__ unsigned part[WAVES];
     __shared__ unsigned pick[2];                                              // the pass's digit, and what is left of K below it
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const unsigned g = blockIdx.x;
     int q_first = table[g * COLS + CFSH_Q0], nq = table[g * COLS + CFSH_NQ];
     if (q_first < 0 || nq < 0 || (long long)q_first + nq > NQ) nq = 0;        // a device table that is not the validated host rows
     unsigned* keys = work + (size_t)g * NC;
     // 1. the group scores, as keys: a thread per column, the queries' rows one after the other (coalesced at every q)
-    for (int c = tid; c < NC; c += WG) {
-        float best = -__builtin_inff();
-        bool any = false;
-        for (int q = 0; q < nq; ++q) {
-            const float v = S[(size_t)(q_first + q) * NC + c];
-            if (v == v) {
-                best = any ? fmaxf(best, v) : v;
-                any = true;
-            }
-        }
-        keys[c] = score_key(best, any);
-    }
+    for (int c = tid; c < NC; c += WG) keys[c] = group_score_key(S, q_first, nq, NC, c);
     __syncthreads();
-    // 2. the K-th largest key, a byte per pass from the top: of the keys that share the bytes found so far, count the next byte's values,
-    // then walk the counts from 255 down until `left` of them are covered
-    unsigned prefix = 0, left = (unsigned)K;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        const unsigned mask = pass ? 0xffffffffu << (shift + 8) : 0u;
-        for (int i = tid; i < WAVES * 256; i += WG) hist[i] = 0;
-        __syncthreads();
-        for (int c = tid; c < NC; c += WG) {
-            const unsigned k = keys[c];
-            if ((k & mask) == prefix) atomicAdd(&hist[wave * 256 + ((k >> shift) & 255u)], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {                                                      // lane l owns the values 4 l .. 4 l + 3
-            unsigned s[4], mine = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[j] = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) s[j] += hist[w * 256 + 4 * lane + j];
-                mine += s[j];
-            }
-            unsigned suffix = mine;                                           // -> the count over this lane's values and all above
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned v = __shfl_down(suffix, o, 64);
-                if (lane + o < 64) suffix += v;
-            }
-            unsigned above = suffix - mine;
-#pragma unroll
-            for (int j = 3; j >= 0; --j) {
-                const unsigned incl = above + s[j];
-                if (above < left && incl >= left) {                           // exactly one (lane, j): left >= 1, and K <= NC keys exist
-                    pick[0] = (unsigned)(4 * lane + j);
-                    pick[1] = left - above;
-                }
-                above = incl;
-            }
-        }
-        __syncthreads();
-        prefix |= pick[0] << shift;
-        left = pick[1];
-    }
-    // prefix is the K-th largest key; `left` of the keys equal to it are kept, the lowest columns first.  A threshold of 0 means fewer
-    // than K columns are selectable: every key above 0 is kept and nothing else.
-    const unsigned thr = prefix, need_eq = thr ? left : 0u;
-    // 3. compaction in ascending column order, WG columns at a time
+    // 2. the K-th largest key; `left` of the keys equal to it are kept, the lowest columns first.  A threshold of 0 means fewer than K
+    // columns are selectable: every key above 0 is kept and nothing else.
+    unsigned left;
+    const unsigned thr = kth_largest_key(keys, NC, (unsigned)K, hist, pick, [&](unsigned cell) { atomicAdd(&hist[cell], 1u); }, left);
+    // 3. compaction in ascending column order, then the padding, at the end
     int32_t* oc = sel_cols + (size_t)g * K;
     int32_t* os = sel_slots + (size_t)g * K;
-    unsigned n_eq = 0, n_out = 0;                                             // equal keys seen, places written: uniform
-    for (int c0 = 0; c0 < NC; c0 += WG) {
-        const int c = c0 + tid;
-        const unsigned k = c < NC ? keys[c] : 0u;
-        const bool gt = k > thr, eq = thr && k == thr;
-        unsigned eq_total, take_total;
-        const unsigned eq_rank = n_eq + block_prefix(eq, part, eq_total);
-        const bool take = gt || (eq && eq_rank < need_eq);
-        const unsigned at = n_out + block_prefix(take, part, take_total);
-        if (take && at < (unsigned)K) {
-            oc[at] = c;
-            os[at] = cols[c];
-        }
-        n_eq += eq_total;
-        n_out += take_total;
-    }
-    for (unsigned r = n_out + tid; r < (unsigned)K; r += WG) {                // padding, at the end
+    const unsigned n_out = compact_selected(keys, NC, (unsigned)K, thr, thr ? left : 0u, part, [&](unsigned at, int c) {
+        oc[at] = c;
+        os[at] = cols[c];
+    });
+    for (unsigned r = n_out + tid; r < (unsigned)K; r += WG) {
         oc[r] = CFSH_NONE;
         os[r] = -1;
     }

@@ -67,6 +67,16 @@ GroupedPackedOutput and StreamOutput with the same tuple contents and that one a
 z: the rule's thresholds are in units of the pair's own deviation and an Event's score and peak are deviations.  baseline(h) lists a
 session's cells.
 
+shortlist=Shortlist(gallery, keep=K) (clip_fsar_amd.shortlist; the pool's LiveGallery), shortlist_hold=H: every session's windows of a push
+are one group of the shortlist's stages -- coarse scores over every class, then the exact kernel on K of them -- and smoothing, baselines
+and the detector run over the selected slot lists.  The selection is libclipfsar_pool_select.so's (clip_fsar_amd.pool_select_hip): a
+(session, class) pair that was scored at the session's previous scoring push stays listed ("pinned") while its event is running or its
+onset streak is counting, and for H further pushes after it was selected on its score; a pair that was not scored at the previous
+scoring push has its marks zeroed by the selection, so it starts anew in all three states, as a newly enrolled class does.  Outputs are
+subclasses of PackedOutput / StreamOutput over the K listed classes with .columns (indices into gallery.class_ids, ascending, NONE = no
+class), .pinned and .class_ids(); stats() gains "pins" and "pins_dropped"; active() and baseline() list the pairs scored at the session's
+last scoring push.  keep >= len(gallery) is the pool without a shortlist, bit for bit.  open(classes=) and enroll(join=True) are refused.
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -87,6 +97,7 @@ from . import events_hip as evhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
+from . import pool_select_hip as pship
 from .baseline import Baseline
 from .events import EventRule, translate
 from .gallery import _GalleryBase
@@ -104,8 +115,8 @@ GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions fi
 def _with_deviation(base):
     """the output type of a pool with a baseline: `base`'s tuple, and the attribute `deviation` beside it"""
     class _Deviating(base):
-        def __new__(cls, *fields, deviation):
-            self = super().__new__(cls, *fields)
+        def __new__(cls, *fields, deviation, **more):
+            self = super().__new__(cls, *fields, **more)
             self.deviation = deviation
             return self
     _Deviating.__name__ = _Deviating.__qualname__ = "Deviation" + base.__name__
@@ -116,13 +127,42 @@ def _with_deviation(base):
 DeviationPackedOutput = _with_deviation(PackedOutput)
 DeviationGroupedPackedOutput = _with_deviation(GroupedPackedOutput)
 DeviationStreamOutput = _with_deviation(StreamOutput)
+
+
+def _with_columns(base):
+    """the output type of a pool with a shortlist: `base`'s tuple -- logits, smoothed (and deviation) are [nW, K] -- and beside it
+    `columns` and `pinned`: int32 on the device, [K] of a session's output and [sessions of the push, K] of a packed one; columns: indices
+    into gallery.class_ids as of the push, ascending, NONE where the list is shorter (every place of a session without windows);
+    pinned: the place's PIN_* bits, 0: selected on its score"""
+    class _Listed(base):
+        def __new__(cls, *fields, columns, pinned, ids):
+            self = super().__new__(cls, *fields)
+            self.columns, self.pinned, self._ids = columns, pinned, ids
+            return self
+
+        def class_ids(self):
+            """the class ids behind `columns` (None where a place holds no class), per session of a packed output.  Synchronises."""
+            rows = self.columns.cpu().tolist()
+            name = lambda row: [self._ids[c] if c != pship.NONE else None for c in row]
+            return name(rows) if self.columns.dim() == 1 else [name(row) for row in rows]
+    _Listed.__name__ = _Listed.__qualname__ = "Shortlist" + base.__name__
+    _Listed.__doc__ = "%s of a pool with a shortlist: the same tuple over the K listed classes, .columns, .pinned and .class_ids()" % base.__name__
+    return _Listed
+
+
+ShortlistPackedOutput = _with_columns(PackedOutput)
+ShortlistStreamOutput = _with_columns(StreamOutput)
+DeviationShortlistPackedOutput = _with_deviation(ShortlistPackedOutput)
+DeviationShortlistStreamOutput = _with_deviation(ShortlistStreamOutput)
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
 Plan = collections.namedtuple("Plan", "rounds first_window n_windows order")
 # What a push with an event rule queues: buf, the device's int32 answer (n_events, then the events and values of events_hip.detect), and
 # the metadata fixed at push time, per table row: the session's handle, its first window of the push and its columns' class ids.
-EventBatch = collections.namedtuple("EventBatch", "buf sessions first_window class_ids")
+# columns: of a pool with a shortlist, the push's sel_cols [rows, K] on the device -- a record's column is a place of that list, and
+# class_ids then holds per row the gallery's class ids of that push, which the place's column indexes; None otherwise.
+EventBatch = collections.namedtuple("EventBatch", "buf sessions first_window class_ids columns", defaults=(None,))
 EVENT_QUEUE = 64                                  # pushes whose records may wait for take_events()
 
 
@@ -193,7 +233,7 @@ def plan_enroll(sessions, requests, T, stride, rate, cap, names=None):
 
 
 class _Session:
-    __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout", "classes")
+    __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout", "classes", "tick")
 
     def __init__(self, slot, classes=None):
         self.slot = slot
@@ -202,14 +242,22 @@ class _Session:
 
     def clear(self):
         self.t = 0                               # frames pushed since open() / reset()
+        self.tick = 0                            # scoring pushes (pushes that completed a window) since then: a shortlist pool's clock
         self.tower_frames = 0
         self.state_gen = None                    # generation of the pool's smoothing buffer this session's state row was written in
         self.state_layout = None                 # the gallery's layout_version then (None: a gallery whose columns never change meaning)
 
 
 class StreamPool:
-    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column", events=None,
-                 baseline=None):
+    def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
+                 *positional, shortlist=None, shortlist_hold=None, events=None, baseline=None):
+        # shortlist= and shortlist_hold= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+        # existed and still are: `positional` takes them, so no earlier call changes its meaning.
+        if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
+            raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
+                            "by keyword as well; got %d positional" % (8 + len(positional)))
+        events = positional[0] if positional else events
+        baseline = positional[1] if len(positional) > 1 else baseline
         if not isinstance(gallery, _GalleryBase):
             raise TypeError("StreamPool: gallery must be a SupportGallery or a TextGallery, got %s" % type(gallery).__name__)
         for name, v in (("max_streams", max_streams), ("stride", stride), ("rate", rate), ("max_push", max_push)):
@@ -251,6 +299,23 @@ class StreamPool:
                                  "keyed by column, the baseline's by class")
             if max_streams * gallery.capacity > blhip.MAX_CELLS:
                 raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "baseline="))
+        if shortlist is None and shortlist_hold is not None:
+            raise ValueError("StreamPool: shortlist_hold = %r is given without shortlist= -- there is no list to hold a class in"
+                             % (shortlist_hold,))
+        if shortlist is not None:
+            from .shortlist import Shortlist
+            if not isinstance(shortlist, Shortlist):
+                raise TypeError("StreamPool: shortlist must be a Shortlist, got %s" % type(shortlist).__name__)
+            if shortlist.gallery is not gallery:
+                raise ValueError("StreamPool: shortlist= was built over another gallery -- shortlist.gallery must be the pool's gallery")
+            if smooth and smooth_by == "column":
+                raise ValueError("StreamPool: shortlist= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
+                                 "keyed by column, and a shortlist's columns change with every push")
+            hold = 0 if shortlist_hold is None else shortlist_hold
+            if isinstance(hold, bool) or not isinstance(hold, int) or not 0 <= hold <= pship.MAX_HOLD:
+                raise ValueError("StreamPool: shortlist_hold must be an integer in [0, 2^20], got %r" % (shortlist_hold,))
+            if max_streams * gallery.capacity > pship.MAX_CELLS:
+                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "shortlist="))
         self.smooth_by = smooth_by
         self._by_class = smooth_by == "class" and bool(smooth)     # with smooth = 0 the option is inert
         self.gallery = gallery
@@ -281,6 +346,15 @@ class StreamPool:
             self._ev_queue = collections.deque() # EventBatch per push that ran the detector, oldest first
             self._ev_ready = []                  # Events of batches a push had to translate itself
             self._ev_ids = (None, None)          # (layout_version, class count) and the gallery's class ids then
+        self._shortlist = shortlist              # the Shortlist, or None: nothing below is there
+        if shortlist is not None:
+            self._hold = hold
+            self._totals.update(pins=0, pins_dropped=0)
+            self._sl_planes = None               # (seen, merit), each [max_streams, store capacity] int32
+            self._sl_unmarked = set()            # the slots whose rows of both planes are to be zeroed, as _unmarked
+            self._sl_tables = None               # pool_select_hip's group tables, made by the first scoring push
+            self._sl_pins = None                 # [2] int64 on the device: pins and dropped pins of the pushes not yet read
+            self._ev_ids = (None, None)          # _every_class_ids' cache, with or without a rule: the ids behind a push's columns
         self._baseline = baseline                # the Baseline, or None: nothing below is there
         if baseline is not None:
             self._bl_cells = None                # (mean, dev, count, marks), each [max_streams, store capacity]
@@ -295,6 +369,9 @@ class StreamPool:
     def open(self, classes=None):
         """a new session, its frames numbered from 0 -> its handle.  classes: registered class ids (any order, no repeats) -- the session
         is scored against these alone, its logits' columns in the order given; None: every class, in registration order."""
+        if classes is not None and self._shortlist is not None:
+            raise ValueError("StreamPool: open(classes=) on a pool with shortlist= is not supported -- per-session candidate lists are "
+                             "out of scope; every session is shortlisted from every class")
         if classes is not None:
             classes = list(classes)
             if not hasattr(self.gallery, "classify_features_grouped"):
@@ -316,6 +393,8 @@ class StreamPool:
             self._ev_unmarked.add(self._sessions[h].slot)
         if self._baseline is not None:
             self._bl_unmarked.add(self._sessions[h].slot)
+        if self._shortlist is not None:
+            self._sl_unmarked.add(self._sessions[h].slot)
         return h
 
     def _session_lists(self, handles, lists):
@@ -346,6 +425,8 @@ class StreamPool:
             self._ev_unmarked.add(s.slot)
         if self._baseline is not None:
             self._bl_unmarked.add(s.slot)
+        if self._shortlist is not None:
+            self._sl_unmarked.add(s.slot)
 
     @property
     def sessions(self):
@@ -353,8 +434,12 @@ class StreamPool:
 
     def stats(self, h=None):
         """of a session: frames, tower_frames and windows since open() / reset(); of the pool: what all pushes added up to, and the open
-        sessions -- with an event rule also "events" and "events_dropped", the records translated so far and those beyond max_events"""
+        sessions -- with an event rule also "events" and "events_dropped", the records translated so far and those beyond max_events;
+        with a shortlist also "pins" and "pins_dropped", the pinned (session, class) pairs the selections counted and those of them that
+        more than K pins squeezed out (reading them synchronises)"""
         if h is None:
+            if self._shortlist is not None:
+                self._read_pins()
             return dict(self._totals, open=len(self._sessions))
         s = self._session(h)
         return {"frames": s.t, "tower_frames": s.tower_frames, "windows": window_plan(0, s.t, self.T, self.stride, self.rate)[1]}
@@ -451,6 +536,11 @@ class StreamPool:
             else:
                 block = lambda t: t[w0:w1]
             fields = (po.first_window[i], block(po.logits), None if po.smoothed is None else block(po.smoothed))
+            if hasattr(po, "columns"):              # of a pool with a shortlist: the session's row of the lists
+                more = dict(columns=po.columns[i], pinned=po.pinned[i], ids=po._ids)
+                out[h] = (ShortlistStreamOutput(*fields, **more) if deviation is None
+                          else DeviationShortlistStreamOutput(*fields, deviation=block(deviation), **more))
+                continue
             out[h] = StreamOutput(*fields) if deviation is None else DeviationStreamOutput(*fields, deviation=block(deviation))
         return out
 
@@ -662,7 +752,7 @@ class StreamPool:
             return []
         at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
         gens = self.gallery.slot_generations().index_select(0, at)
-        valid = (marks[s.slot].index_select(0, at) == gens).tolist()
+        valid = ((marks[s.slot].index_select(0, at) == gens) & self._listed(s, at)).tolist()
         cols = [t[s.slot].index_select(0, at).tolist() for t in (mean, dev, count)]
         return [(c, m, d, n) for c, live, m, d, n in zip(ids, valid, *cols) if live]
 
@@ -693,9 +783,10 @@ class StreamPool:
             self._ev_ids = (key, tuple(g.class_ids))
         return self._ev_ids[1]
 
-    def _detect(self, handles, recs, plan, scores, cp):
+    def _detect(self, handles, recs, plan, scores, cp, columns=None):
         """one cfev_detect over the push's session-major scores (three launches, no synchronisation); the records stay on the device and
-        are queued with the push's metadata"""
+        are queued with the push's metadata.  columns: of a shortlist push, its sel_cols -- handles, recs and plan.first_window then hold
+        the sessions with windows alone, the table's rows"""
         rule = self._events
         cplan, gens, keys, table = cp
         cells = self._event_cells(gens.shape[0])
@@ -715,7 +806,7 @@ class StreamPool:
             if s.classes is None:
                 every = self._every_class_ids() if every is None else every
             ids.append(every if s.classes is None else s.classes)       # a session's list is replaced (enroll's join), never changed
-        self._ev_queue.append(EventBatch(buf, handles, plan.first_window, ids))
+        self._ev_queue.append(EventBatch(buf, handles, plan.first_window, ids, columns))
 
     @staticmethod
     def _records(buf, M):
@@ -728,13 +819,27 @@ class StreamPool:
         if not batches:
             return []
         M = self._events.max_events
-        host = (batches[0].buf[None] if len(batches) == 1 else torch.stack([b.buf for b in batches])).cpu()
+        if self._shortlist is None:
+            host = (batches[0].buf[None] if len(batches) == 1 else torch.stack([b.buf for b in batches])).cpu()
+            lists = [None] * len(batches)
+        else:                                      # the pushes' columns ride behind their records, and the pin counters (two int64 as
+            pieces = [t.reshape(-1) for b in batches for t in (b.buf, b.columns)]       # four int32) behind them: still one copy
+            counted, self._sl_pins = self._sl_pins, None
+            if counted is not None:
+                pieces.append(counted.view(torch.int32))
+            parts = torch.cat(pieces).cpu().split([t.numel() for t in pieces])
+            if counted is not None:
+                self._count_pins(*parts[-1].clone().view(torch.int64).tolist())
+            host, lists = parts[0:2 * len(batches):2], [c.view(len(b.sessions), -1).tolist() for b, c in zip(batches, parts[1::2])]
         out, dropped = [], 0
-        for b, h in zip(batches, host):
+        for b, h, columns in zip(batches, host, lists):
             n = int(h[0])
             kept = min(n, M)
             events, values = self._records(h, M)
-            out.extend(translate(events[:kept], values[:kept], kept, b.sessions, b.first_window, b.class_ids, self._events))
+            ids = b.class_ids
+            if columns is not None:                # a record's column is a place of the push's list: the class behind it then
+                ids = [[every[c] if c != pship.NONE else None for c in row] for every, row in zip(ids, columns)]
+            out.extend(translate(events[:kept], values[:kept], kept, b.sessions, b.first_window, ids, self._events))
             self._totals["events"] += kept
             dropped += n - kept
         if dropped:
@@ -749,7 +854,7 @@ class StreamPool:
 
     def take_events(self):
         """the Events of every push since the last call, push by push; within a push in session order as pushed, then window, then
-        column.  Synchronises once; clears the queue."""
+        column.  Synchronises once; clears the queue.  (Of a pool with a shortlist the pin counters come down in the same copy.)"""
         self._need_rule("take_events")
         batches = list(self._ev_queue)
         self._ev_queue.clear()
@@ -771,11 +876,13 @@ class StreamPool:
             return []
         at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
         gens = self.gallery.slot_generations().index_select(0, at)
-        on = ((marks[s.slot].index_select(0, at) == gens) & (streak[s.slot].index_select(0, at) < 0)).tolist()
+        on = ((marks[s.slot].index_select(0, at) == gens) & (streak[s.slot].index_select(0, at) < 0) & self._listed(s, at)).tolist()
         lens, peaks = length[s.slot].index_select(0, at).tolist(), peak[s.slot].index_select(0, at).tolist()
         return [(c, n, p) for c, live, n, p in zip(ids, on, lens, peaks) if live]
 
     def _run(self, eng, feats, handles, recs, counts):
+        if self._shortlist is not None:
+            return self._run_shortlist(eng, feats, handles, recs, counts)
         if any(s.classes is not None for s in recs):
             return self._run_grouped(eng, feats, handles, recs, counts)
         g, T, C = self.gallery, self.T, len(self.gallery)
@@ -818,6 +925,158 @@ class StreamPool:
         self._totals["windows"] += NW
         fields = (handles, plan.first_window, offsets, logits, smoothed)
         return PackedOutput(*fields) if self._baseline is None else DeviationPackedOutput(*fields, deviation=deviation)
+
+    # ------------------------------------------------------------------ the pool with a shortlist
+    def _shortlist_planes(self, cap):
+        """seen and merit, each [max_streams, cap] int32, grown with the store as _class_state grows its own: the columns copied, the new
+        columns 0 (never scored); the rows of sessions opened or reset since the last push are zeroed here, on the push's stream"""
+        if self.max_streams * cap > pship.MAX_CELLS:
+            raise ValueError(self._too_many_cells(self.max_streams, cap, "shortlist="))
+        old = None if self._sl_planes is None else self._sl_planes[0].shape[1]
+        if old != cap:
+            new = tuple(torch.zeros(self.max_streams, cap, device=self.dev, dtype=torch.int32) for _ in range(2))
+            if old is not None:
+                for t, was in zip(new, self._sl_planes):
+                    t[:, :old].copy_(was)
+            self._sl_planes = new
+        for slot in sorted(self._sl_unmarked):
+            for t in self._sl_planes:
+                t[slot].zero_()
+        self._sl_unmarked.clear()
+        return self._sl_planes
+
+    def _listed(self, s, at):
+        """of a pool with a shortlist: which of the session's cells at the store slots `at` (a device index) were scored at its last
+        scoring push -- active() and baseline() list those alone; without a shortlist: all of them"""
+        if self._shortlist is None:
+            return torch.ones(at.shape[0], device=self.dev, dtype=torch.bool)
+        if self._sl_planes is None or s.slot in self._sl_unmarked or not s.tick:
+            return torch.zeros(at.shape[0], device=self.dev, dtype=torch.bool)
+        inside = at < self._sl_planes[0].shape[1]
+        return inside & (self._sl_planes[0][s.slot].index_select(0, at.clamp(max=self._sl_planes[0].shape[1] - 1)) == s.tick)
+
+    def _read_pins(self):
+        """the device's pin counts of the pushes since the last reading -> the totals.  Synchronises."""
+        if self._sl_pins is not None:
+            counted, self._sl_pins = self._sl_pins, None
+            self._count_pins(*counted.tolist())
+
+    def _count_pins(self, pins, dropped):
+        self._totals["pins"] += pins
+        self._totals["pins_dropped"] += dropped
+
+    def _run_shortlist(self, eng, feats, handles, recs, counts):
+        """_run of a pool with a shortlist: every window of the push is gathered into one session-major buffer, each session's windows
+        are one group of the Shortlist's stages with cfps_select_pinned in the place of cfsh_select, and smoothing, baselines and the
+        detector run over the selected slot lists [G, K] as their keys -> ShortlistPackedOutput"""
+        g, T, sl = self.gallery, self.T, self._shortlist
+        plan = plan_push([(s.slot, s.t) for s in recs], counts, T, self.stride, self.rate, self.max_push)
+        NW = sum(plan.n_windows)
+        live = [i for i, nW in enumerate(plan.n_windows) if nW]               # the sessions with a group, in the order pushed
+        # ---- what the host decides and sends up before the first launch
+        K = min(sl.keep, len(g))
+        if NW:
+            prep = sl._pool_prepare()
+            gens = g.slot_generations()
+            order = None if plan.order is None else torch.tensor(plan.order, device=self.dev)
+            n_live = [plan.n_windows[i] for i in live]
+            sel_rows, _ = pship.table_rows(n_live, [recs[i].slot for i in live], [recs[i].tick + 1 for i in live])
+            chunks = -(-K // cship.CHUNK)
+            key_rows = [[recs[i].slot, nW, q * K, K, j * K, j * chunks] for j, (i, nW, q) in enumerate(zip(live, n_live, (
+                r[pship.Q0] for r in sel_rows)))]                             # plan_rows' shape: NC = K, KEY0 = j * K
+            cplan = cship.SmoothPlan(key_rows, [], False, NW * K, len(live) * chunks)
+        every = self._every_class_ids()          # cached until the classes change: no O(classes) work per tick
+        # ---- the device: ring writes and gathers, round by round
+        W = torch.empty(NW, T, self.E, device=self.dev, dtype=torch.float32)
+        g0 = 0
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+            W[g0 + w0:g0 + w1].copy_(X)
+            if w1 == nW:
+                g0 += nW
+        offsets = [0]
+        for nW in plan.n_windows:
+            offsets.append(offsets[-1] + nW)
+        S_push = len(recs)
+        columns = torch.full((S_push, K), pship.NONE, device=self.dev, dtype=torch.int32)
+        pinned = torch.zeros(S_push, K, device=self.dev, dtype=torch.int32)
+        logits = torch.empty(NW, K, device=self.dev, dtype=torch.float32)
+        smoothed = torch.empty_like(logits) if self._by_class else None
+        deviation = torch.empty_like(logits) if self._baseline is not None else None
+        if NW:
+            if order is not None:                  # several rounds: round-major -> session-major, a group must be consecutive
+                W = W.index_select(0, order)
+            cap = gens.shape[0]
+            seen, merit = self._shortlist_planes(cap)
+            smooth_marks = self._class_state(cap)[1] if self._by_class else None
+            base_marks = self._baseline_cells(cap)[3] if self._baseline is not None else None
+            ev_streak, ev_marks = (self._event_cells(cap)[0], self._event_cells(cap)[3]) if self._events is not None else (None, None)
+            G = len(live)
+            if self._sl_tables is None:
+                self._sl_tables = pship.table_uploader(self.dev, self.max_streams)
+            sel_pin = torch.empty(G, K, device=self.dev, dtype=torch.int32)
+            n_pins = torch.empty(G, device=self.dev, dtype=torch.int32)
+
+            def select(S, cols, K):
+                sel_cols = torch.empty(G, K, device=self.dev, dtype=torch.int32)
+                sel_slots = torch.empty(G, K, device=self.dev, dtype=torch.int32)
+                work = torch.empty(pship.workspace_floats(G, S.shape[1]), device=self.dev, dtype=torch.float32)
+                pship.select_pinned(S, cols, gens, ev_streak, ev_marks, seen, merit, smooth_marks, base_marks,
+                                    self._sl_tables.upload(sel_rows), sl.keep, self._hold, sel_cols, sel_slots, sel_pin, n_pins, work)
+                return sel_cols, sel_slots
+
+            sel_cols, sel_slots, flat, _ = sl._pool_score(prep, W, n_live, select)
+            logits = flat.view(NW, K)
+            for s in (recs[i] for i in live):
+                s.tick += 1
+            if self._smooth_tables is None:
+                self._smooth_tables = cship.table_uploader(self.dev, self.max_streams)
+            cp = (cplan, gens, sel_slots.view(-1), self._smooth_tables.upload(key_rows))
+            if self._by_class:
+                smoothed = self._smooth_classes(cp, logits)
+            judged = smoothed if self._by_class else logits
+            if self._baseline is not None:
+                judged = deviation = self._normalize(cp, judged)
+            if self._events is not None:
+                self._detect([handles[i] for i in live], [recs[i] for i in live], Plan(None, [plan.first_window[i] for i in live], None, None),
+                             judged, cp, columns=sel_cols)
+            if G == S_push:
+                columns, pinned = sel_cols, sel_pin
+            else:
+                for j, i in enumerate(live):     # no index goes up inside a push: the rows are copied one by one
+                    columns[i].copy_(sel_cols[j])
+                    pinned[i].copy_(sel_pin[j])
+            counted = torch.stack([n_pins.sum(), (n_pins - K).clamp_(min=0).sum()])
+            self._sl_pins = counted if self._sl_pins is None else self._sl_pins + counted
+        for s, n in zip(recs, counts):             # the counters move once every stage is enqueued, as in _run
+            s.t += n
+        self._totals["frames"] += sum(counts)
+        self._totals["windows"] += NW
+        fields = (handles, plan.first_window, offsets, logits, smoothed)
+        more = dict(columns=columns, pinned=pinned, ids=every)
+        return (ShortlistPackedOutput(*fields, **more) if self._baseline is None
+                else DeviationShortlistPackedOutput(*fields, deviation=deviation, **more))
+
+    def _topk_shortlist(self, out, k, smoothed):
+        """topk of a shortlist pool's output: the top-k places of every window's row (a place without a class is never taken), mapped
+        to class indices through the session's columns"""
+        src = out.smoothed if smoothed else out.logits
+        if src is None:
+            raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")
+        nW, K = src.shape
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(grhip.TOPK_MAX, K):
+            raise ValueError("StreamPool.topk: k must be in [1, min(16, K = %d = min(keep, number of classes))], got %r" % (K, k))
+        if not nW:
+            return (torch.empty(0, k, device=self.dev, dtype=torch.float32), torch.empty(0, k, device=self.dev, dtype=torch.int32))
+        if out.columns.dim() == 1:                 # a session's output
+            n_windows, lists = [nW], out.columns[None]
+        else:
+            n_windows, lists = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])], out.columns
+        group = torch.tensor([i for i, n in enumerate(n_windows) for _ in range(n)], device=self.dev, dtype=torch.int64)
+        rows, _ = grhip.table_rows(n_windows, [K] * len(n_windows), self.T)
+        values, index = self.gallery.topk_of_groups(src.contiguous().view(-1), rows, k)
+        found = index != pship.NONE
+        place = torch.where(found, index, torch.zeros_like(index)).long()
+        return values, torch.where(found, lists[group].gather(1, place), index)
 
     # ------------------------------------------------------------------ enrolment
     def _enrolling_gallery(self):
@@ -895,6 +1154,9 @@ class StreamPool:
     def enroll(self, h, class_id, window=None, text=None, join=False):
         """enroll_windows([(h, window, class_id)], text) -> the class's shot count.  join=True: a session opened with classes=[...] gets
         the class appended to its list when it is not there (a session without a list sees every class anyway)."""
+        if join and self._shortlist is not None:
+            raise ValueError("StreamPool: enroll(join=True) on a pool with shortlist= is not supported -- per-session candidate lists are "
+                             "out of scope; every session is shortlisted from every class, an enrolled one included")
         shots = self.enroll_windows([(h, window, class_id)], text)
         cid = next(iter(shots))
         s = self._sessions[h]
@@ -921,6 +1183,8 @@ class StreamPool:
         a GroupedPackedOutput, the index counts within that session's list, and k is at most the shortest list of a session with windows."""
         if isinstance(out, GroupedPackedOutput):
             return self._topk_grouped(out, k, smoothed)
+        if hasattr(out, "columns"):                # of a pool with a shortlist: the index counts in gallery.class_ids, NONE where the
+            return self._topk_shortlist(out, k, smoothed)                     # session's list is shorter than k
         src = out.smoothed if smoothed else out.logits
         if src is None:
             raise ValueError("StreamPool.topk: this output has no smoothed scores (smooth = 0)")

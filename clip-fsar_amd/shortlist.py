@@ -88,6 +88,43 @@ def reference_select(S, counts, keep):
     return out
 
 
+def reference_select_pinned(S, counts, keep, pinned):
+    """The selection rule of cfps_select_pinned (include/ext/clipfsar_pool_select.h) on the host.  S, counts, keep: as reference_select;
+    pinned: per group the pinned columns with their bits, {column: bits != 0} (or None: no pins) -> (columns, pins, n_pins): per group
+    the K = min(keep, NC) kept columns in ascending order padded with NONE, their bits (0: kept on its score, and at padded places), and
+    P, the number of pinned columns.  P <= K: every pin is kept whatever its score, the other K - P places go to the best selectable
+    columns that are not pinned (reference_select's order).  P > K: the K best pins, the larger score first and the lower column on equal
+    scores, a pin that is not selectable below every score by lower column.  A group without clips keeps nothing and counts no pin."""
+    rows = S.tolist() if hasattr(S, "tolist") else [list(r) for r in S]
+    counts = list(counts)
+    if sum(counts) != len(rows):
+        raise ValueError("reference_select_pinned: the counts add up to %d, S has %d rows" % (sum(counts), len(rows)))
+    if len(pinned) != len(counts):
+        raise ValueError("reference_select_pinned: %d groups, pins for %d" % (len(counts), len(pinned)))
+    NC = len(rows[0]) if rows else 0
+    K = min(int(keep), NC)
+    columns, pins, n_pins, q = [], [], [], 0
+    for n, pin in zip(counts, pinned):
+        pin = dict(pin or {}) if n else {}
+        if any(not 0 <= c < NC or not bits for c, bits in pin.items()):
+            raise ValueError("reference_select_pinned: a pin names a column outside [0, %d) or carries no bit: %r" % (NC, pin))
+        score = {}                                             # the selectable columns' group scores
+        for c, column in enumerate(zip(*rows[q:q + n])):
+            vals = [v for v in column if v == v]
+            if vals and max(vals) > float("-inf"):
+                score[c] = max(vals)
+        q += n
+        if len(pin) <= K:
+            free = sorted((-v, c) for c, v in score.items() if c not in pin)[:K - len(pin)]
+            kept = sorted(list(pin) + [c for _, c in free])
+        else:                                                  # (0, -score, column) before (1, column): a pin without a score is last
+            kept = sorted(sorted(pin, key=lambda c: (0, -score[c], c) if c in score else (1, 0.0, c))[:K])
+        columns.append(kept + [NONE] * (K - len(kept)))
+        pins.append([pin.get(c, 0) for c in kept] + [0] * (K - len(kept)))
+        n_pins.append(len(pin))
+    return columns, pins, n_pins
+
+
 # ---------------------------------------------------------------------------------------------------------------- the class
 class ShortlistResult:
     """logits [N, K] fp32, columns [G, K] int32 (device; indices into the call's candidate list, ascending, NONE = no class), keep = K,
@@ -103,6 +140,7 @@ class ShortlistResult:
 
 
 _Plan = collections.namedtuple("_Plan", "eng ids slots K counts N")
+_PoolPrep = collections.namedtuple("_PoolPrep", "eng ids K cols pending")
 
 
 class Shortlist:
@@ -126,15 +164,25 @@ class Shortlist:
         self.stats = {"calls": 0, "refreshed": 0}
 
     # ------------------------------------------------------------------ what a call decides before the device is touched
+    def _ready(self):
+        """the gallery's engine, fresh, and at least one class"""
+        eng = self.gallery._fresh_engine()
+        if not self.gallery._ids:
+            raise RuntimeError("Shortlist: no classes registered")
+        return eng
+
+    def _every_class(self):
+        """(the slots of all the gallery's classes, their ids): the lists are kept while the gallery's book is the same one"""
+        g = self.gallery
+        if self._all[0] is not g._book:
+            self._all = (g._book, plan_columns(g._book), list(g._book.order))
+        return self._all[1], self._all[2]
+
     def _plan(self, src, tower, counts, classes, k=None):
         g = self.gallery
-        eng = g._fresh_engine()
-        if not g._ids:
-            raise RuntimeError("Shortlist: no classes registered")
-        if classes is None:                                # every class: the lists are kept while the gallery's book is the same one
-            if self._all[0] is not g._book:
-                self._all = (g._book, plan_columns(g._book), list(g._book.order))
-            _, slots, ids = self._all
+        eng = self._ready()
+        if classes is None:
+            slots, ids = self._every_class()
         else:
             ids = list(classes)
             slots = plan_columns(g._book, ids, "Shortlist")
@@ -269,6 +317,26 @@ class Shortlist:
         found = index != NONE
         place = torch.where(found, index, torch.zeros_like(index)).long()
         return values, torch.where(found, sel_cols[group].gather(1, place), index)
+
+    # ------------------------------------------------------------------ the entry of StreamPool(shortlist=...)
+    def _pool_prepare(self):
+        """The host half of a pool's push, before its first launch: the candidates are every registered class.  -> _PoolPrep(eng, ids,
+        K, cols: the candidates' slots on the device, pending: _stale's answer).  Every list made on the host goes up here."""
+        g = self.gallery
+        eng = self._ready()
+        slots, ids = self._every_class()
+        return _PoolPrep(eng, ids, min(self.keep, len(slots)), g._columns(None), self._stale(slots))
+
+    def _pool_score(self, prep, X, counts, select):
+        """The device half: X [NW, T, E], the tower features of the push's windows, group-major (counts[i] consecutive windows per group)
+        -> (sel_cols, sel_slots [G, K] on the device, the flat logits, the table rows of the grouped launch).  _run's stages with
+        select(S, cols, K) -> (sel_cols, sel_slots) -- the pool's pinned selection -- in the place of _select.  Only enqueues."""
+        Xq, qn = self._queries(prep.eng, X, False)
+        S = self._coarse_scores(Xq, qn, prep.pending, prep.cols)
+        sel_cols, sel_slots = select(S, prep.cols, prep.K)
+        flat, rows = self._exact(Xq, qn, sel_slots, counts, prep.K)
+        self.stats["calls"] += 1
+        return sel_cols, sel_slots, flat, rows
 
     # ------------------------------------------------------------------ the public calls
     def classify(self, queries, counts=None, classes=None):
