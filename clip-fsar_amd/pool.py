@@ -18,6 +18,8 @@
                                            # shot of a registered one) out of the ring's tower rows: the tower does not run.  Needs a LiveGallery
     p.enrolable(a)                         # range of the window numbers still in the ring; p.enroll(a, 7, window=w, join=True)
     p.enroll_windows([(a, None, 7), (b, 3, 7), (b, 4, "kite")], text={"kite": "flying a kite"})     # -> {7: 2, "kite": 1}
+    p.explain(a, classes=[7], window=None) # the OTAM soft alignment of one window still in the ring against class 7 (or k=3: against its own
+                                           # top 3): clip_fsar_amd.align.Alignment; changes nothing of the session.  Needs a LiveGallery
     p.reset(a); p.close(a); p.stats(a); p.stats()
     q = StreamPool(live_gallery, smooth=0.5, smooth_by="class")      # smoothing state per (session, class) instead of per column: class
     c = q.open(classes=[9, 2]); q.enroll(c, "kite", join=True)        # lists, enrolment and removals while sessions run, no reset()
@@ -1163,6 +1165,23 @@ class StreamPool:
         if join and s.classes is not None and cid not in s.classes:
             s.classes = s.classes + [cid]
         return shots[cid]
+
+    # ------------------------------------------------------------------ explanation
+    def explain(self, h, classes=None, k=None, window=None):
+        """The OTAM soft alignment of one window of the session (window: a number of enrolable(h); None: the newest complete one) against
+        `classes` (registered ids) or against its own top-k classes -> clip_fsar_amd.align.Alignment of one clip: per class the T x T plan,
+        the cosine distances and the logit.  The window's T tower rows are read out of the ring, as enroll() reads them, and go through
+        Aligner.align_features; nothing of the session changes -- ring, counters, smoothing, baselines, detector and shortlist planes stay
+        as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring."""
+        from .align import Aligner
+        s = self._session(h)
+        al = getattr(self, "_aligner", None)
+        if al is None or al.gallery is not self.gallery:
+            al = self._aligner = Aligner(self.gallery)
+        ap = al._plan(1, classes, k)                                          # every error before the device is touched
+        plan = plan_enroll([(s.slot, s.t)], [(0, window)], self.T, self.stride, self.rate, self.cap, names=["StreamPool: session %d" % h])
+        rows = torch.tensor([(plan.positions[0] + j * self.rate) % self.cap for j in range(self.T)], device=self.dev)
+        return al._run(ap, self.gallery._check_feats(self._ring[s.slot].index_select(0, rows).unsqueeze(0)), False)
 
     # ------------------------------------------------------------------ top-k
     def _topk_grouped(self, out, k, smoothed):
