@@ -218,7 +218,7 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
 # (clip_fsar_amd.align).  ExtLib values again; the open registry.
 PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
                             os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
-               for name in ("baseline", "shortlist", "pool_select", "align")}
+               for name in ("baseline", "shortlist", "pool_select", "align", "tempo")}
 
 
 def plugin_lib_names() -> list:

@@ -29,6 +29,9 @@
     z = StreamPool(live_gallery, baseline=Baseline(rate=1 / 32, warmup=16, gate=3.0), events=EventRule(on=4, off=2, min_on=2, min_off=2))
     z.push_features({a: fa})[a].deviation                             # [nW, C]: (score - the pair's mean) / its deviation; the rule judges it
     z.baseline(a)                                                     # [(class_id, mean, dev, n)] of the session's baselines
+    t = StreamPool(live_gallery, stride=2, rates=(1, 2, 3))           # every window scored at three frame rates, the best one kept
+    o = t.push_features({a: fa})[a]; o.logits, o.tempo, o.rates       # [nW, C] fp32, [nW, C] int32 (index into rates), (1, 2, 3)
+    t.enroll(a, "kite", tempo=0); t.explain(a, [7], tempo=1)          # a window of the ring read at rates[0] / rates[1]
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -79,6 +82,18 @@ subclasses of PackedOutput / StreamOutput over the K listed classes with .column
 class), .pinned and .class_ids(); stats() gains "pins" and "pins_dropped"; active() and baseline() list the pairs scored at the session's
 last scoring push.  keep >= len(gallery) is the pool without a shortlist, bit for bit.  open(classes=) and enroll(join=True) are refused.
 
+rates=(r_0 < .. < r_{R-1}) (1 to 8 integers; a SupportGallery or a LiveGallery; `rate` stays at its default): the pool plans, sizes its
+ring and numbers its windows exactly as a pool with rate = rmax = r_{R-1}.  Window k is completed by frame e_k = k * stride + (T - 1) *
+rmax, and its TEMPO i is the T frames e_k - (T - 1 - j) * r_i, j < T: every tempo ends on the window's newest frame, so all complete in
+the same push, and tempo R - 1 is the window of the rate = rmax pool.  The tower runs once per frame as before; per chunk of windows one
+gather reads the R sequences of every window out of the ring (libclipfsar_tempo.so, clip_fsar_amd.tempo_hip, over the pool's own
+descriptor table), classify_features scores them, and one launch reduces the R scores of every (window, class) cell to their maximum --
+`logits` -- and the index of the tempo that gave it -- `tempo`, int32 in the layout of logits; ties go to the lowest index, and a NaN
+among the R scores stays a NaN (reference_reduce restates the rule).  Smoothing, baselines, the detector, topk and stats() run on the
+reduced scores unchanged.  The outputs are subclasses of PackedOutput / StreamOutput (and of their Deviation forms) with .tempo and
+.rates.  enroll, enroll_windows and explain take tempo=, the index into rates at which a window of the ring is read (None: the last).
+open(classes=) and shortlist= are refused, and so is a TextGallery or LiveTextGallery.
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -100,6 +115,7 @@ from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
 from . import pool_select_hip as pship
+from . import tempo_hip as tphip
 from .baseline import Baseline
 from .events import EventRule, translate
 from .gallery import _GalleryBase
@@ -156,6 +172,25 @@ ShortlistPackedOutput = _with_columns(PackedOutput)
 ShortlistStreamOutput = _with_columns(StreamOutput)
 DeviationShortlistPackedOutput = _with_deviation(ShortlistPackedOutput)
 DeviationShortlistStreamOutput = _with_deviation(ShortlistStreamOutput)
+
+
+def _with_tempo(base):
+    """the output type of a pool with rates=: `base`'s tuple, and beside it `tempo` -- int32 on the device in the layout of .logits, per
+    cell the index into `rates` of the tempo whose score .logits holds -- and `rates`, the pool's tuple"""
+    class _Tempo(base):
+        def __new__(cls, *fields, tempo, rates):
+            self = super().__new__(cls, *fields)
+            self.tempo, self.rates = tempo, rates
+            return self
+    _Tempo.__name__ = _Tempo.__qualname__ = "Tempo" + base.__name__
+    _Tempo.__doc__ = "%s of a pool with rates=: the same tuple, .tempo in the layout of .logits and .rates" % base.__name__
+    return _Tempo
+
+
+TempoPackedOutput = _with_tempo(PackedOutput)
+TempoStreamOutput = _with_tempo(StreamOutput)
+DeviationTempoPackedOutput = _with_deviation(TempoPackedOutput)
+DeviationTempoStreamOutput = _with_deviation(TempoStreamOutput)
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
@@ -234,6 +269,32 @@ def plan_enroll(sessions, requests, T, stride, rate, cap, names=None):
     return EnrollPlan(windows, slots, positions)
 
 
+def tempo_positions(win_pos, w, stride, T, rates, cap):
+    """The ring rows of every tempo of window w of a table row whose WIN_POS is win_pos (the first frame of the row's first window in its
+    rmax = rates[-1] form): [[row of frame j, j < T] per tempo i].  Tempo i holds the frames e - (T - 1 - j) * rates[i] with e the frame
+    that completes the window, so its first frame lies (T - 1) * (rmax - rates[i]) behind the rmax form's first."""
+    rmax = rates[-1]
+    return [[(win_pos + w * stride + (T - 1) * (rmax - r) + j * r) % cap for j in range(T)] for r in rates]
+
+
+def reference_reduce(scores, R):
+    """cftp_reduce in torch (CPU tensors too): scores [NW * R, C], rows ordered (window, tempo) -> (out [NW, C], tempo [NW, C] int32).
+    Per cell the largest of the R scores and the lowest index that holds it; when one of them is NaN, the first NaN and its index.  out
+    is one of the inputs bit for bit."""
+    scores = torch.as_tensor(scores, dtype=torch.float32)
+    if scores.dim() != 2 or R < 1 or scores.shape[0] % R:
+        raise ValueError("reference_reduce: scores must be [NW * R, C] with R = %d >= 1, got %s" % (R, tuple(scores.shape)))
+    s = scores.view(scores.shape[0] // R, R, scores.shape[1])
+    best = s[:, 0].clone()
+    at = torch.zeros(best.shape, dtype=torch.int32, device=scores.device)
+    for i in range(1, R):
+        v = s[:, i]
+        better = ~torch.isnan(best) & ((v > best) | torch.isnan(v))
+        best = torch.where(better, v, best)
+        at = torch.where(better, torch.full_like(at, i), at)
+    return best, at
+
+
 class _Session:
     __slots__ = ("slot", "t", "tower_frames", "state_gen", "state_layout", "classes", "tick")
 
@@ -252,8 +313,8 @@ class _Session:
 
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
-                 *positional, shortlist=None, shortlist_hold=None, events=None, baseline=None):
-        # shortlist= and shortlist_hold= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+                 *positional, shortlist=None, shortlist_hold=None, rates=None, events=None, baseline=None):
+        # shortlist=, shortlist_hold= and rates= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
             raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
@@ -267,6 +328,8 @@ class StreamPool:
                 raise ValueError("StreamPool: %s must be an integer >= 1, got %r" % (name, v))
         if max_streams > php.MAX_STREAMS:
             raise ValueError("StreamPool: max_streams = %d, the pool library serves at most %d" % (max_streams, php.MAX_STREAMS))
+        if rates is not None:
+            rates, rate = self._check_rates(gallery, rates, rate, shortlist), rates[-1]
         smooth = float(smooth)
         if not 0.0 <= smooth < 1.0:
             raise ValueError("StreamPool: smooth must be in [0, 1), got %r" % smooth)
@@ -323,6 +386,7 @@ class StreamPool:
         self.gallery = gallery
         self.dev = gallery.dev
         self.max_streams, self.stride, self.rate, self.max_push, self.alpha = max_streams, stride, rate, max_push, smooth
+        self.rates = rates                       # the tempo pool's rates, ascending (self.rate is the largest of them), or None
         self.T, self.E = gallery.T, gallery.E
         self.cap = (self.T - 1) * rate + max_push
         self._ring = torch.empty(max_streams, self.cap, self.E, device=self.dev, dtype=torch.float32)
@@ -367,10 +431,38 @@ class StreamPool:
             ingest.serves(self.dev, who="StreamPool")
         self._ingest = ingest                    # push_u8's transform; None: built from gallery.head.args by the first push_u8
 
+    @staticmethod
+    def _check_rates(gallery, rates, rate, shortlist):
+        """rates= of the constructor -> the tuple; every refusal of the option, before anything is allocated"""
+        from .live_text_gallery import LiveTextGallery
+        from .text_gallery import TextGallery
+        if isinstance(rates, (str, bytes)) or not isinstance(rates, (tuple, list)):
+            raise TypeError("StreamPool: rates must be a tuple of integers, got %s" % type(rates).__name__)
+        if rate != 1:
+            raise ValueError("StreamPool: rates= is given together with rate = %d -- leave rate at its default, the pool plans with the "
+                             "largest of rates" % rate)
+        if not 1 <= len(rates) <= tphip.MAX_RATES:
+            raise ValueError("StreamPool: rates holds %d values -- give 1 to %d frame rates" % (len(rates), tphip.MAX_RATES))
+        for r in rates:
+            if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+                raise ValueError("StreamPool: rates must hold integers >= 1, got %r in %r" % (r, tuple(rates)))
+        if any(b <= a for a, b in zip(rates, rates[1:])):
+            raise ValueError("StreamPool: rates must be strictly ascending, got %r -- sort them and drop repeats" % (tuple(rates),))
+        if isinstance(gallery, (TextGallery, LiveTextGallery)):
+            raise ValueError("StreamPool: rates= on a %s is not supported -- a maximum over per-tempo softmax probabilities is another "
+                             "quantity; use a SupportGallery or a LiveGallery" % type(gallery).__name__)
+        if shortlist is not None:
+            raise ValueError("StreamPool: rates= together with shortlist= is not supported -- tempo windows of a shortlisted pool are out "
+                             "of scope; build the pool with one of the two")
+        return tuple(rates)
+
     # ------------------------------------------------------------------ sessions
     def open(self, classes=None):
         """a new session, its frames numbered from 0 -> its handle.  classes: registered class ids (any order, no repeats) -- the session
         is scored against these alone, its logits' columns in the order given; None: every class, in registration order."""
+        if classes is not None and self.rates is not None:
+            raise ValueError("StreamPool: open(classes=) on a pool with rates= is not supported -- per-session class lists with tempo "
+                             "windows are out of scope; open the session without a list")
         if classes is not None and self._shortlist is not None:
             raise ValueError("StreamPool: open(classes=) on a pool with shortlist= is not supported -- per-session candidate lists are "
                              "out of scope; every session is shortlisted from every class")
@@ -531,6 +623,7 @@ class StreamPool:
         """PackedOutput or GroupedPackedOutput -> {session: StreamOutput}"""
         out = {}
         deviation = getattr(po, "deviation", None)      # of a pool with a baseline: each session's StreamOutput carries its block too
+        tempo = getattr(po, "tempo", None)              # of a pool with rates=: likewise its block of the tempo plane
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
             if isinstance(po, GroupedPackedOutput):
@@ -542,6 +635,11 @@ class StreamPool:
                 more = dict(columns=po.columns[i], pinned=po.pinned[i], ids=po._ids)
                 out[h] = (ShortlistStreamOutput(*fields, **more) if deviation is None
                           else DeviationShortlistStreamOutput(*fields, deviation=block(deviation), **more))
+                continue
+            if tempo is not None:
+                more = dict(tempo=block(tempo), rates=po.rates)
+                out[h] = (TempoStreamOutput(*fields, **more) if deviation is None
+                          else DeviationTempoStreamOutput(*fields, deviation=block(deviation), **more))
                 continue
             out[h] = StreamOutput(*fields) if deviation is None else DeviationStreamOutput(*fields, deviation=block(deviation))
         return out
@@ -589,9 +687,11 @@ class StreamPool:
     def _gathered(self, eng, plan, feats):
         """The device side of a push up to scoring: per round one table and one ring write, then per chunk of its windows one gather.
         Yields (round, its table, its windows nW, chunk w0, w1, the chunk's windows X [w1 - w0, T, E]); a round without windows yields
-        nothing."""
+        nothing.  Of a pool with rates=: X is [(w1 - w0) * R, T, E], the R tempos of every window, rows ordered (window, tempo), and a
+        chunk holds as many windows as their R sequences each fit classify_features."""
         T = self.T
-        per = max(1, eng.max_frames // T)        # classify_features scores that many clips per chunk: gather no more at a time
+        R = 1 if self.rates is None else len(self.rates)
+        per = max(1, eng.max_frames // (T * R))  # classify_features scores that many clips per chunk: gather no more at a time
         for rnd in plan.rounds:
             if len(plan.rounds) == 1:
                 piece = feats
@@ -602,12 +702,15 @@ class StreamPool:
             nW = sum(r[php.NW] for r in rnd.rows)
             if nW == 0:
                 continue
-            if self._X is None or self._X.shape[0] < min(nW, per):
-                self._X = torch.empty(min(nW, per), T, self.E, device=self.dev, dtype=torch.float32)
+            if self._X is None or self._X.shape[0] < min(nW, per) * R:
+                self._X = torch.empty(min(nW, per) * R, T, self.E, device=self.dev, dtype=torch.float32)
             for w0 in range(0, nW, per):
                 w1 = min(nW, w0 + per)
-                X = self._X[:w1 - w0]
-                php.window_sequences(self._ring, X, table, nW, w0, w1, T, self.stride, self.rate)
+                X = self._X[:(w1 - w0) * R]
+                if self.rates is None:
+                    php.window_sequences(self._ring, X, table, nW, w0, w1, T, self.stride, self.rate)
+                else:
+                    tphip.window_sequences(self._ring, X, table, nW, w0, w1, T, self.stride, self.rates)
                 yield rnd, table, nW, w0, w1, X
 
     def _run_grouped(self, eng, feats, handles, recs, counts):
@@ -893,13 +996,17 @@ class StreamPool:
         NW = sum(plan.n_windows)
         logits = torch.empty(NW, C, device=self.dev, dtype=torch.float32)
         smoothed = torch.empty_like(logits) if by_column else None
+        tempo = torch.empty(NW, C, device=self.dev, dtype=torch.int32) if self.rates is not None else None
         if by_column and NW and (self._state is None or self._state.shape[1] != C):
             self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
             self._state_gen += 1
         g0 = 0
         for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
             out = logits[g0:g0 + nW]
-            out[w0:w1].copy_(g.classify_features(X))
+            if tempo is None:
+                out[w0:w1].copy_(g.classify_features(X))
+            else:                                # the R scores of every (window, class) cell -> their maximum and the tempo that gave it
+                tphip.reduce(g.classify_features(X), out[w0:w1], tempo[g0 + w0:g0 + w1], len(self.rates))
             if w1 == nW:                         # the round's last chunk
                 if by_column:
                     php.smooth_logits(out, self._state, smoothed[g0:g0 + nW], table, self.alpha)
@@ -908,6 +1015,7 @@ class StreamPool:
             index = torch.tensor(plan.order, device=self.dev)
             logits = logits.index_select(0, index)
             smoothed = smoothed.index_select(0, index) if by_column else None
+            tempo = tempo.index_select(0, index) if tempo is not None else None
         cp = self._class_push(recs, plan.n_windows) if self._keyed and NW else None
         if self._by_class:                       # one launch, on the session-major logits: a session's rounds stay in sequence
             smoothed = self._smooth_classes(cp, logits)
@@ -926,6 +1034,10 @@ class StreamPool:
         self._totals["frames"] += sum(counts)
         self._totals["windows"] += NW
         fields = (handles, plan.first_window, offsets, logits, smoothed)
+        if tempo is not None:
+            more = dict(tempo=tempo, rates=self.rates)
+            return (TempoPackedOutput(*fields, **more) if self._baseline is None
+                    else DeviationTempoPackedOutput(*fields, deviation=deviation, **more))
         return PackedOutput(*fields) if self._baseline is None else DeviationPackedOutput(*fields, deviation=deviation)
 
     # ------------------------------------------------------------------ the pool with a shortlist
@@ -1093,22 +1205,42 @@ class StreamPool:
         self._enrolling_gallery()
         return enrolable_windows(self._session(h).t, self.T, self.stride, self.rate, self.cap)
 
-    def _ring_sequences(self, trows, slots, positions, classes):
-        """one launch: the support sequences X0 [n, T+1, E] of the ring windows (slot, position), each closed by trows[classes[i]]"""
+    def _tempo(self, tempo, what):
+        """tempo= of enroll / enroll_windows / explain -> (the rate the window is read at, how far its first frame lies behind the first
+        frame of the window as enrolable(h) numbers it)"""
+        if self.rates is None:
+            if tempo is not None:
+                raise ValueError("StreamPool.%s: tempo = %r on a pool without rates= -- build the pool with rates=(...) or leave tempo "
+                                 "at None" % (what, tempo))
+            return self.rate, 0
+        R = len(self.rates)
+        if tempo is None:
+            tempo = R - 1
+        if isinstance(tempo, bool) or not isinstance(tempo, int) or not 0 <= tempo < R:
+            raise ValueError("StreamPool.%s: tempo must be an index into rates = %r, 0 .. %d, or None (the last one), got %r"
+                             % (what, self.rates, R - 1, tempo))
+        return self.rates[tempo], (self.T - 1) * (self.rate - self.rates[tempo])
+
+    def _ring_sequences(self, trows, slots, positions, classes, rate=None):
+        """one launch: the support sequences X0 [n, T+1, E] of the ring windows (slot, position), each closed by trows[classes[i]];
+        rate: the frames' distance in the ring (None: the pool's)"""
         n = len(slots)
         if self._enroll_tables is None or self._enroll_tables.max_rows < n:
             self._enroll_tables = enhip.table_uploader(self.dev, max(1024, n))
         X0 = torch.empty(n, self.T + 1, self.E, device=self.dev, dtype=torch.float32)
-        enhip.ring_sequences(self._ring, trows, self._enroll_tables.upload(enhip.table_rows(slots, positions, classes)), X0, self.rate)
+        enhip.ring_sequences(self._ring, trows, self._enroll_tables.upload(enhip.table_rows(slots, positions, classes)), X0,
+                             self.rate if rate is None else rate)
         return X0
 
-    def enroll_windows(self, items, text=None):
+    def enroll_windows(self, items, text=None, tempo=None):
         """items: [(session, window number or None: the session's newest complete window, class id), ...] -> {class id: its shot count}.
         Every window becomes a shot of its class: of a registered class a further one (LiveGallery.add_shots' rules), of an unknown id
         the first of a new class (add_classes' rules; its text from TEST.CLASS_NAME or from `text`).  Several windows of one class are its
-        shots in the order given.  The windows' tower rows are read out of the ring -- one launch for the new classes, one for the further
+        shots in the order given.  tempo (a pool with rates=): the index into rates at which every window of the call is read; None:
+        the last one, the window as enrolable(h) numbers it.  The windows' tower rows are read out of the ring -- one launch for the new classes, one for the further
         shots -- and the tower does not run.  Every error is raised before any launch and leaves the gallery as it was."""
         g = self._enrolling_gallery()
+        rate, shift = self._tempo(tempo, "enroll_windows")
         eng = g._fresh_engine()
         items = list(items) if isinstance(items, (list, tuple)) else None
         if not items or any(not isinstance(it, (list, tuple)) or len(it) != 3 for it in items):
@@ -1141,8 +1273,10 @@ class StreamPool:
             offs = [0]
             for c in classes:
                 offs.append(offs[-1] + sum(1 for i in members if ids[i] == c))
-            return lambda trows: (self._ring_sequences(trows, [plan.slots[i] for i in order], [plan.positions[i] for i in order],
-                                                       [local[ids[i]] for i in order]), offs)
+            at_tempo = () if self.rates is None else (rate,)                  # a pool without rates= calls it as it always did
+            return lambda trows: (self._ring_sequences(trows, [plan.slots[i] for i in order],
+                                                       [(plan.positions[i] + shift) % self.cap for i in order],
+                                                       [local[ids[i]] for i in order], *at_tempo), offs)
 
         result = {}
         if known:
@@ -1153,13 +1287,13 @@ class StreamPool:
             result.update(zip(new_ids, counts))
         return {c: result[c] for c in dict.fromkeys(ids)}
 
-    def enroll(self, h, class_id, window=None, text=None, join=False):
-        """enroll_windows([(h, window, class_id)], text) -> the class's shot count.  join=True: a session opened with classes=[...] gets
+    def enroll(self, h, class_id, window=None, text=None, join=False, tempo=None):
+        """enroll_windows([(h, window, class_id)], text, tempo) -> the class's shot count.  join=True: a session opened with classes=[...] gets
         the class appended to its list when it is not there (a session without a list sees every class anyway)."""
         if join and self._shortlist is not None:
             raise ValueError("StreamPool: enroll(join=True) on a pool with shortlist= is not supported -- per-session candidate lists are "
                              "out of scope; every session is shortlisted from every class, an enrolled one included")
-        shots = self.enroll_windows([(h, window, class_id)], text)
+        shots = self.enroll_windows([(h, window, class_id)], text, tempo)
         cid = next(iter(shots))
         s = self._sessions[h]
         if join and s.classes is not None and cid not in s.classes:
@@ -1167,20 +1301,22 @@ class StreamPool:
         return shots[cid]
 
     # ------------------------------------------------------------------ explanation
-    def explain(self, h, classes=None, k=None, window=None):
+    def explain(self, h, classes=None, k=None, window=None, tempo=None):
         """The OTAM soft alignment of one window of the session (window: a number of enrolable(h); None: the newest complete one) against
         `classes` (registered ids) or against its own top-k classes -> clip_fsar_amd.align.Alignment of one clip: per class the T x T plan,
         the cosine distances and the logit.  The window's T tower rows are read out of the ring, as enroll() reads them, and go through
         Aligner.align_features; nothing of the session changes -- ring, counters, smoothing, baselines, detector and shortlist planes stay
-        as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring."""
+        as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring.  tempo (a
+        pool with rates=): the index into rates at which the window is read; None: the last one."""
         from .align import Aligner
         s = self._session(h)
+        rate, shift = self._tempo(tempo, "explain")
         al = getattr(self, "_aligner", None)
         if al is None or al.gallery is not self.gallery:
             al = self._aligner = Aligner(self.gallery)
         ap = al._plan(1, classes, k)                                          # every error before the device is touched
         plan = plan_enroll([(s.slot, s.t)], [(0, window)], self.T, self.stride, self.rate, self.cap, names=["StreamPool: session %d" % h])
-        rows = torch.tensor([(plan.positions[0] + j * self.rate) % self.cap for j in range(self.T)], device=self.dev)
+        rows = torch.tensor([(plan.positions[0] + shift + j * rate) % self.cap for j in range(self.T)], device=self.dev)
         return al._run(ap, self.gallery._check_feats(self._ring[s.slot].index_select(0, rows).unsqueeze(0)), False)
 
     # ------------------------------------------------------------------ top-k
