@@ -32,6 +32,9 @@
     t = StreamPool(live_gallery, stride=2, rates=(1, 2, 3))           # every window scored at three frame rates, the best one kept
     o = t.push_features({a: fa})[a]; o.logits, o.tempo, o.rates       # [nW, C] fp32, [nW, C] int32 (index into rates), (1, 2, 3)
     t.enroll(a, "kite", tempo=0); t.explain(a, [7], tempo=1)          # a window of the ring read at rates[0] / rates[1]
+    v = StreamPool(live_gallery, events=EventRule(on=0.6, off=0.4), evidence=Evidence(capacity=256))     # clip_fsar_amd.evidence
+    e = v.take_events()[0]; v.held(e); v.evidence_features(e)         # an EvidenceEvent; its window's [T, E] rows, long after the ring moved on
+    v.explain_event(e); v.enroll_event(e, "kite")                     # explain / enroll on the kept rows, whatever became of the session
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -94,6 +97,16 @@ reduced scores unchanged.  The outputs are subclasses of PackedOutput / StreamOu
 .rates.  enroll, enroll_windows and explain take tempo=, the index into rates at which a window of the ring is read (None: the last).
 open(classes=) and shortlist= are refused, and so is a TextGallery or LiveTextGallery.
 
+evidence=Evidence(capacity, kinds) (clip_fsar_amd.evidence; needs events=): the push that detects an event of one of `kinds` also copies
+the T ring rows of the event's window into a slot of a device store (libclipfsar_evidence.so, clip_fsar_amd.evidence_hip: two launches
+right behind the detector's, driven by its records on the device, no synchronisation; with rates= the window is read at the tempo that
+won the event's cell).  take_events() then returns EvidenceEvents -- Event's fields, then `evidence` (the capture's serial, or None),
+`missed` (None, "ring": a later round of the same push had overwritten the window, "capacity": more than `capacity` captures in one
+push, "kind") and `tempo` -- and still synchronises once: the capture's answers come down with the records.  Serial s lives in slot
+s mod capacity and is held until `capacity` later captures have overwritten it, through close(), reset() and any number of pushes;
+held(e), evidence_features(e), explain_event(e) and enroll_event(e, class_id) work on it (each first translates the queued pushes, its
+one synchronisation; take_events() still returns their events).  stats() gains "evidence" and "evidence_missed".
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -110,6 +123,7 @@ import torch
 from . import baseline_hip as blhip
 from . import class_smooth_hip as cship
 from . import enroll_hip as enhip
+from . import evidence_hip as edhip
 from . import events_hip as evhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
@@ -118,6 +132,7 @@ from . import pool_select_hip as pship
 from . import tempo_hip as tphip
 from .baseline import Baseline
 from .events import EventRule, translate
+from .evidence import MISSED, Evidence, EvidenceEvent, keep0
 from .gallery import _GalleryBase
 from .ingest import FrameIngest
 from .stream import StreamOutput, window_plan
@@ -313,8 +328,8 @@ class _Session:
 
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
-                 *positional, shortlist=None, shortlist_hold=None, rates=None, events=None, baseline=None):
-        # shortlist=, shortlist_hold= and rates= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, events=None, baseline=None):
+        # shortlist=, shortlist_hold=, rates= and evidence= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
             raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
@@ -353,6 +368,12 @@ class StreamPool:
                                  "keyed by column, the detector's by class")
             if max_streams * gallery.capacity > evhip.MAX_CELLS:
                 raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "events="))
+        if evidence is not None:
+            if not isinstance(evidence, Evidence):
+                raise TypeError("StreamPool: evidence must be an Evidence, got %s" % type(evidence).__name__)
+            if events is None:
+                raise ValueError("StreamPool: evidence= is given without events= -- evidence is the window behind an event; build the "
+                                 "pool with events=EventRule(...) as well")
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
@@ -412,6 +433,14 @@ class StreamPool:
             self._ev_queue = collections.deque() # EventBatch per push that ran the detector, oldest first
             self._ev_ready = []                  # Events of batches a push had to translate itself
             self._ev_ids = (None, None)          # (layout_version, class count) and the gallery's class ids then
+        self._evidence = evidence                # the Evidence, or None: nothing below is there
+        if evidence is not None:
+            self._totals.update(evidence=0, evidence_missed=0)
+            self._ed_store = None                # [capacity, T, E] fp32, with _ed_head [1] int32 and _ed_work: made by the first push that detects
+            self._ed_head = self._ed_work = self._ed_tables = None
+            self._ed_captured = 0                # captures translated so far: the next serial
+            # the type of this pool's events: EvidenceEvent under its own name, so that an event says which pool's store holds its window
+            self._event_type = type("EvidenceEvent", (EvidenceEvent,), {"__slots__": (), "__doc__": EvidenceEvent.__doc__})
         self._shortlist = shortlist              # the Shortlist, or None: nothing below is there
         if shortlist is not None:
             self._hold = hold
@@ -530,7 +559,8 @@ class StreamPool:
         """of a session: frames, tower_frames and windows since open() / reset(); of the pool: what all pushes added up to, and the open
         sessions -- with an event rule also "events" and "events_dropped", the records translated so far and those beyond max_events;
         with a shortlist also "pins" and "pins_dropped", the pinned (session, class) pairs the selections counted and those of them that
-        more than K pins squeezed out (reading them synchronises)"""
+        more than K pins squeezed out (reading them synchronises); with evidence= also "evidence" and "evidence_missed", the windows
+        captured and those that had left the ring or found no room, counted as "events" is, when the records are translated"""
         if h is None:
             if self._shortlist is not None:
                 self._read_pins()
@@ -748,7 +778,7 @@ class StreamPool:
         if self._baseline is not None:
             judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, judged, cp)
+            self._detect(handles, recs, plan, judged, cp, after=[s.t for s in recs])     # the counters have moved already
         fields = (handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
         return GroupedPackedOutput(*fields) if self._baseline is None else DeviationGroupedPackedOutput(*fields, deviation=deviation)
 
@@ -888,10 +918,11 @@ class StreamPool:
             self._ev_ids = (key, tuple(g.class_ids))
         return self._ev_ids[1]
 
-    def _detect(self, handles, recs, plan, scores, cp, columns=None):
+    def _detect(self, handles, recs, plan, scores, cp, columns=None, after=None, tempo=None):
         """one cfev_detect over the push's session-major scores (three launches, no synchronisation); the records stay on the device and
         are queued with the push's metadata.  columns: of a shortlist push, its sel_cols -- handles, recs and plan.first_window then hold
-        the sessions with windows alone, the table's rows"""
+        the sessions with windows alone, the table's rows.  after, tempo (a pool with evidence=): the frames each session will have
+        after this push and the push's tempo plane -- the capture follows the detector on the same stream."""
         rule = self._events
         cplan, gens, keys, table = cp
         cells = self._event_cells(gens.shape[0])
@@ -899,10 +930,13 @@ class StreamPool:
         if self._ev_work is None or self._ev_work.shape[0] < need:
             self._ev_work = torch.empty(need, device=self.dev, dtype=torch.int32)
         M = rule.max_events
-        buf = torch.empty(1 + (evhip.EVENT_COLS + evhip.VALUE_COLS) * M, device=self.dev, dtype=torch.int32)
+        n_where = 0 if self._evidence is None else 2 * M      # the capture's `where` rides behind the records: one copy brings both down
+        buf = torch.empty(1 + (evhip.EVENT_COLS + evhip.VALUE_COLS) * M + n_where, device=self.dev, dtype=torch.int32)
         events, values = self._records(buf, M)
         evhip.detect(scores.view(-1), *cells, gens, keys, events, values, buf[:1], self._ev_work, table, rule.on, rule.off, rule.min_on,
                      rule.min_off)
+        if self._evidence is not None:
+            self._capture(plan.first_window, cplan.rows, after, events, buf[:1], self._where(buf, M), tempo)
         if len(self._ev_queue) >= EVENT_QUEUE:     # a full queue: the oldest batch is translated here and kept for take_events()
             self._ev_ready.extend(self._translate([self._ev_queue.popleft()]))
         every = None
@@ -917,7 +951,29 @@ class StreamPool:
     def _records(buf, M):
         """the events [M, 5] int32 and values [M, 2] fp32 inside an EventBatch's buffer (buf[0] is n_events)"""
         split = 1 + evhip.EVENT_COLS * M
-        return buf[1:split].view(M, evhip.EVENT_COLS), buf[split:].view(torch.float32).view(M, evhip.VALUE_COLS)
+        return buf[1:split].view(M, evhip.EVENT_COLS), buf[split:split + evhip.VALUE_COLS * M].view(torch.float32).view(M, evhip.VALUE_COLS)
+
+    @staticmethod
+    def _where(buf, M):
+        """of a pool with evidence=: the capture's where [M, 2] int32 behind the records of an EventBatch's buffer"""
+        return buf[1 + (evhip.EVENT_COLS + evhip.VALUE_COLS) * M:].view(M, 2)
+
+    def _capture(self, first_window, rows, after, events, n_events, where, tempo):
+        """one cfed_capture behind the detector (two launches, no synchronisation): the windows of the push's records of the Evidence's
+        kinds go into the store.  rows: the detector's table rows; first_window, after: per row the session's first window of the push
+        and its frames once the push is done, which say where the row's windows lie in the ring and which of them a later round of the
+        same push has overwritten."""
+        ev = self._evidence
+        if self._ed_store is None:
+            self._ed_store = torch.empty(ev.capacity, self.T, self.E, device=self.dev, dtype=torch.float32)
+            self._ed_head = torch.zeros(1, device=self.dev, dtype=torch.int32)
+            self._ed_work = torch.empty(edhip.workspace_ints(ev.capacity), device=self.dev, dtype=torch.int32)
+            self._ed_tables = edhip.table_uploader(self.dev, self.max_streams)
+        table = [[r[evhip.SLOT], (first * self.stride) % self.cap, r[evhip.NW], keep0(first, r[evhip.NW], self.stride, t, self.cap),
+                  r[evhip.OUT0], r[evhip.NC]] for r, first, t in zip(rows, first_window, after)]
+        more = {} if self.rates is None else dict(rates=self.rates)
+        edhip.capture(self._ring, events, n_events, None if self.rates is None else tempo.view(-1), self._ed_store, self._ed_head, where,
+                      self._ed_work, self._ed_tables.upload(table), ev.mask, self.stride, self.rate, **more)
 
     def _translate(self, batches):
         """EventBatches -> their Events, batch by batch; one synchronising copy"""
@@ -944,7 +1000,8 @@ class StreamPool:
             ids = b.class_ids
             if columns is not None:                # a record's column is a place of the push's list: the class behind it then
                 ids = [[every[c] if c != pship.NONE else None for c in row] for every, row in zip(ids, columns)]
-            out.extend(translate(events[:kept], values[:kept], kept, b.sessions, b.first_window, ids, self._events))
+            found = translate(events[:kept], values[:kept], kept, b.sessions, b.first_window, ids, self._events)
+            out.extend(found if self._evidence is None else self._with_evidence(found, events[:kept].tolist(), self._where(h, M)[:kept].tolist()))
             self._totals["events"] += kept
             dropped += n - kept
         if dropped:
@@ -985,6 +1042,95 @@ class StreamPool:
         lens, peaks = length[s.slot].index_select(0, at).tolist(), peak[s.slot].index_select(0, at).tolist()
         return [(c, n, p) for c, live, n, p in zip(ids, on, lens, peaks) if live]
 
+    # ------------------------------------------------------------------ event evidence
+    def _with_evidence(self, found, records, where):
+        """the Events of one batch (translate's order) -> this pool's EvidenceEvents.  records, where: the batch's kept records and the
+        capture's answers, in the device's record order -- the order in which the captures took their slots, so the order of the serials"""
+        serial = {}
+        for i, (slot, _) in enumerate(where):
+            if slot >= 0:
+                if slot != self._ed_captured % self._evidence.capacity:
+                    raise RuntimeError("StreamPool: capture %d took slot %d of the evidence store, the host counted it into slot %d -- "
+                                       "the device's head and the host's count have parted" % (
+                                           self._ed_captured, slot, self._ed_captured % self._evidence.capacity))
+                serial[i] = self._ed_captured
+                self._ed_captured += 1
+            elif slot in (edhip.LEFT_RING, edhip.NO_ROOM):
+                self._totals["evidence_missed"] += 1
+        self._totals["evidence"] += len(serial)
+        # translate sorts the records by (row, window, column) with a stable sort: the same sort over their indices pairs them up
+        order = sorted(range(len(records)), key=lambda i: (records[i][0], records[i][2], records[i][1]))
+        tempo = self.rates is not None
+        return [self._event_type(*e, serial.get(i), None if i in serial else MISSED[where[i][0]], where[i][1] if tempo and i in serial else None)
+                for e, i in zip(found, order)]
+
+    def _held_event(self, e, what):
+        """every refusal of an event method; drains the queued batches (one synchronisation) so that the host's count of captures is the
+        device's -> the event's store slot"""
+        if self._evidence is None:
+            raise ValueError("StreamPool.%s: this pool keeps no evidence (build it with events=EventRule(...), evidence=Evidence(...))" % what)
+        if type(e) is not self._event_type:
+            raise TypeError("StreamPool.%s: takes an EvidenceEvent that this pool's take_events() returned, got %s%s" % (
+                what, type(e).__name__, " of another pool" if isinstance(e, EvidenceEvent) else ""))
+        if e.evidence is None:
+            why = {"ring": "its window had left the ring when the push that detected it ended (a push of several rounds)",
+                   "capacity": "the push that detected it captured more than capacity = %d windows" % self._evidence.capacity,
+                   "kind": "evidence is kept for %s events, this one is an %s" % (" and ".join(self._evidence.kinds), e.kind)}[e.missed]
+            raise ValueError("StreamPool.%s: the event has no evidence (missed = %r): %s" % (what, e.missed, why))
+        batches = list(self._ev_queue)
+        self._ev_queue.clear()
+        self._ev_ready.extend(self._translate(batches))         # take_events() returns them later
+        cap = self._evidence.capacity
+        if isinstance(e.evidence, bool) or not isinstance(e.evidence, int) or not 0 <= e.evidence < self._ed_captured:
+            raise ValueError("StreamPool.%s: evidence %r is not a serial this pool has handed out (%d so far)" % (
+                what, e.evidence, self._ed_captured))
+        if self._ed_captured - e.evidence > cap:
+            raise ValueError("StreamPool.%s: evidence %d is no longer held -- %d windows were captured since, the store keeps the newest "
+                             "capacity = %d; build the pool with a larger Evidence(capacity=)" % (
+                                 what, e.evidence, self._ed_captured - 1 - e.evidence, cap))
+        return e.evidence % cap
+
+    def held(self, e):
+        """whether the event's window is in the store: it was captured, and fewer than `capacity` windows were captured since.
+        Synchronises once when pushes are queued (their events stay for take_events())."""
+        try:
+            self._held_event(e, "held")
+        except ValueError:
+            if self._evidence is None:
+                raise
+            return False
+        return True
+
+    def evidence_features(self, e):
+        """[T, E] fp32, a copy: the tower rows of the event's window as they were in the ring when the event was detected"""
+        slot = self._held_event(e, "evidence_features")
+        return self._ed_store[slot].clone()
+
+    def explain_event(self, e, classes=None, k=None):
+        """explain() of an event's evidence: the OTAM soft alignment of its window against `classes` (default: the event's own class) or
+        against its top-k classes -> clip_fsar_amd.align.Alignment of one clip, through Aligner.align_features.  Changes nothing."""
+        from .align import Aligner
+        slot = self._held_event(e, "explain_event")
+        al = getattr(self, "_aligner", None)
+        if al is None or al.gallery is not self.gallery:
+            al = self._aligner = Aligner(self.gallery)
+        if classes is None and k is None:
+            classes = [e.class_id]
+        return al.align_features(self._ed_store[slot].clone().unsqueeze(0), classes, k)
+
+    def enroll_event(self, e, class_id, text=None):
+        """enroll() of an event's evidence: its window becomes a shot of class_id -- of a registered class a further one, of an unknown id
+        the first of a new class (its text from TEST.CLASS_NAME or from `text`, {class id: name or [E] row}) -> the class's shot count.
+        Through the gallery's add_shots_features / add_classes_features; nothing of any session changes."""
+        slot = self._held_event(e, "enroll_event")
+        g = self._enrolling_gallery()
+        cid = g._shot_ids([class_id])[0]
+        feats = self._ed_store[slot].clone().unsqueeze(0)
+        if cid in g._book.slot_of:
+            return list(g.add_shots_features(feats, [cid]))[0]
+        g.add_classes_features(feats, [cid], text)
+        return 1
+
     def _run(self, eng, feats, handles, recs, counts):
         if self._shortlist is not None:
             return self._run_shortlist(eng, feats, handles, recs, counts)
@@ -1023,7 +1169,7 @@ class StreamPool:
         if self._baseline is not None:           # likewise one launch per push, after smoothing and before the detector
             judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, judged, cp)
+            self._detect(handles, recs, plan, judged, cp, after=[s.t + n for s, n in zip(recs, counts)], tempo=tempo)
         offsets = [0]
         for s, n, nW in zip(recs, counts, plan.n_windows):
             s.t += n
@@ -1152,7 +1298,7 @@ class StreamPool:
                 judged = deviation = self._normalize(cp, judged)
             if self._events is not None:
                 self._detect([handles[i] for i in live], [recs[i] for i in live], Plan(None, [plan.first_window[i] for i in live], None, None),
-                             judged, cp, columns=sel_cols)
+                             judged, cp, columns=sel_cols, after=[recs[i].t + counts[i] for i in live])
             if G == S_push:
                 columns, pinned = sel_cols, sel_pin
             else:
@@ -1306,7 +1452,8 @@ class StreamPool:
         `classes` (registered ids) or against its own top-k classes -> clip_fsar_amd.align.Alignment of one clip: per class the T x T plan,
         the cosine distances and the logit.  The window's T tower rows are read out of the ring, as enroll() reads them, and go through
         Aligner.align_features; nothing of the session changes -- ring, counters, smoothing, baselines, detector and shortlist planes stay
-        as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring.  tempo (a
+        as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring (explain_event(e) of a pool
+        with evidence= has no such limit).  tempo (a
         pool with rates=): the index into rates at which the window is read; None: the last one."""
         from .align import Aligner
         s = self._session(h)
