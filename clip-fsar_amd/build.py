@@ -216,10 +216,11 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
 # The plug-in tier (the comment above SIDE_LIBS): adaptive baselines of the stream pool, the coarse stage of two-stage scoring
 # (clip_fsar_amd.shortlist), the pinned selection of a stream pool with a shortlist, and the OTAM soft alignment behind a score
 # (clip_fsar_amd.align), the tempo windows of a stream pool with rates=, and event evidence (clip_fsar_amd.evidence): an event's
-# window copied out of the ring into a device store by the push that detected it.  ExtLib values again; the open registry.
+# window copied out of the ring into a device store by the push that detected it, and the still-frame gate of a stream pool with
+# still= (clip_fsar_amd.still): frames that did not change skip the tower.  ExtLib values again; the open registry.
 PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
                             os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
-               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence")}
+               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still")}
 
 
 def plugin_lib_names() -> list:

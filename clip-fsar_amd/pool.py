@@ -35,6 +35,8 @@
     v = StreamPool(live_gallery, events=EventRule(on=0.6, off=0.4), evidence=Evidence(capacity=256))     # clip_fsar_amd.evidence
     e = v.take_events()[0]; v.held(e); v.evidence_features(e)         # an EvidenceEvent; its window's [T, E] rows, long after the ring moved on
     v.explain_event(e); v.enroll_event(e, "kite")                     # explain / enroll on the kept rows, whatever became of the session
+    w = StreamPool(gallery, still=StillGate())                        # clip_fsar_amd.still: frames that repeat their predecessor skip the tower
+    w.push({a: frames}); w.last_kept()                                # {a: (True, False, ..)}: which frames went through the tower
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -107,6 +109,16 @@ s mod capacity and is held until `capacity` later captures have overwritten it, 
 held(e), evidence_features(e), explain_event(e) and enroll_event(e, class_id) work on it (each first translates the queued pushes, its
 one synchronisation; take_events() still returns their events).  stats() gains "evidence" and "evidence_missed".
 
+still=StillGate(pixel_tol, changed, max_run) (clip_fsar_amd.still, which states the measure, the predecessor and the rule): a pixel push
+(push, push_packed, push_u8, push_u8_packed) first counts, per frame, the elements that differ from the frame before it by more than
+pixel_tol (libclipfsar_still.so, clip_fsar_amd.still_hip); frames with at most changed * L such elements skip the tower and take the
+tower row of their predecessor -- within the push, or the ring row of the session's newest frame before it.  The counts come to the host
+(the gate's one synchronisation per push: the tower call is sized there), plan_still decides, the kept frames are packed, the tower runs
+on them alone, their rows are expanded to a row per frame, and _run receives what push_features_packed would: rounds, rates=, shortlist=,
+smoothing, baselines, events, evidence, enrolment and explain see no difference, and frame numbers stay.  open(), reset() and a feature
+push leave a session without a predecessor: its next frame goes through the tower whatever it holds.  stats() gains "still_frames",
+tower_frames counts the frames the tower really saw, last_kept() tells them apart.  One frame geometry per pool.
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -129,12 +141,14 @@ from . import gallery_hip as ghip
 from . import groups_hip as grhip
 from . import pool_hip as php
 from . import pool_select_hip as pship
+from . import still_hip as skhip
 from . import tempo_hip as tphip
 from .baseline import Baseline
 from .events import EventRule, translate
 from .evidence import MISSED, Evidence, EvidenceEvent, keep0
 from .gallery import _GalleryBase
 from .ingest import FrameIngest
+from .still import StillGate, plan_still
 from .stream import StreamOutput, window_plan
 
 PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
@@ -328,7 +342,7 @@ class _Session:
 
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
-                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, events=None, baseline=None):
+                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, events=None, baseline=None):
         # shortlist=, shortlist_hold=, rates= and evidence= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
@@ -374,6 +388,8 @@ class StreamPool:
             if events is None:
                 raise ValueError("StreamPool: evidence= is given without events= -- evidence is the window behind an event; build the "
                                  "pool with events=EventRule(...) as well")
+        if still is not None and not isinstance(still, StillGate):
+            raise TypeError("StreamPool: still must be a StillGate, got %s" % type(still).__name__)
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
@@ -454,6 +470,16 @@ class StreamPool:
         if baseline is not None:
             self._bl_cells = None                # (mean, dev, count, marks), each [max_streams, store capacity]
             self._bl_unmarked = set()            # the slots whose row of the baselines' marks is to be zeroed, as _unmarked
+        self._still = still                      # the StillGate, or None: nothing below is there
+        if still is not None:
+            self._totals.update(still_frames=0)
+            self._sk_prev = None                 # [max_streams, L] fp32: every session's newest frame of its last pixel push; made by the first gated push
+            self._sk_hw = None                   # the H x W the store was made for
+            self._sk_state = {}                  # handle -> [has a predecessor in _sk_prev, run of skipped frames, still frames]
+            self._sk_tables = php.TableUploader(self.dev, max_streams, cols=skhip.TABLE_COLS)
+            self._sk_lists = skhip.ListUploader(self.dev)
+            self._sk_work = None                 # still_hip.changed's workspace, grown on demand
+            self._sk_last = {}                   # last_kept()'s answer
         if ingest is not None and not isinstance(ingest, FrameIngest):
             raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
         if ingest is not None:
@@ -510,6 +536,8 @@ class StreamPool:
         h = self._next_handle
         self._next_handle += 1
         self._sessions[h] = _Session(heapq.heappop(self._free), classes)
+        if self._still is not None:
+            self._sk_state[h] = [False, 0, 0]    # no predecessor: the frame a previous owner of the slot left in the store is never read
         if self._by_class:
             self._unmarked.add(self._sessions[h].slot)      # nothing of the slot's previous owner is read
         if self._events is not None:
@@ -537,11 +565,15 @@ class StreamPool:
         """the session's slot becomes free; its handle is never valid again"""
         heapq.heappush(self._free, self._session(h).slot)
         del self._sessions[h]
+        if self._still is not None:
+            del self._sk_state[h]
 
     def reset(self, h):
         """Frame counter 0; the session's ring contents and smoothing state are dropped."""
         s = self._session(h)
         s.clear()
+        if self._still is not None:
+            self._sk_state[h] = [False, 0, 0]
         if self._by_class:
             self._unmarked.add(s.slot)
         if self._events is not None:
@@ -561,6 +593,10 @@ class StreamPool:
         with a shortlist also "pins" and "pins_dropped", the pinned (session, class) pairs the selections counted and those of them that
         more than K pins squeezed out (reading them synchronises); with evidence= also "evidence" and "evidence_missed", the windows
         captured and those that had left the ring or found no room, counted as "events" is, when the records are translated"""
+        if h is not None and self._still is not None:
+            s = self._session(h)
+            return {"frames": s.t, "tower_frames": s.tower_frames, "windows": window_plan(0, s.t, self.T, self.stride, self.rate)[1],
+                    "still_frames": self._sk_state[h][2]}
         if h is None:
             if self._shortlist is not None:
                 self._read_pins()
@@ -619,6 +655,8 @@ class StreamPool:
         windows they complete.  The tower runs once per frame, in one call sequence over all of them."""
         eng = self._ready()
         frames, recs, counts = self._check(frames, (3, None, None), "frames", "[N, 3, H, W]", sessions, counts)
+        if self._still is not None:
+            return self._push_still(eng, frames, list(sessions), recs, counts)
         feats = torch.empty(frames.shape[0], self.E, device=self.dev, dtype=torch.float32)
         for f0 in range(0, frames.shape[0], eng.max_frames):
             f1 = min(frames.shape[0], f0 + eng.max_frames)
@@ -628,10 +666,80 @@ class StreamPool:
         self._totals["tower_frames"] += frames.shape[0]
         return self._run(eng, feats, list(sessions), recs, counts)
 
+    def _push_still(self, eng, frames, handles, recs, counts):
+        """push_packed of a pool with still= (clip_fsar_amd.still): the change count of every frame against its predecessor on the
+        device, plan_still on the host -- counts.cpu() is the gate's ONE synchronisation per push: the tower call has to be sized on the
+        host --, the kept frames packed and the store of newest frames updated in one launch, the tower over the kept frames alone,
+        their rows expanded to a row per frame (a skipped frame before the push's first kept one reads the ring row of the session's
+        newest frame, before _run writes the ring), and _run on the full [N, E] features, as push_features_packed would receive them."""
+        gate = self._still
+        N, (H, W) = frames.shape[0], frames.shape[2:]
+        L = 3 * H * W
+        if L > skhip.MAX_L:
+            raise ValueError("StreamPool: still= keeps a frame of 3 x %d x %d = %d elements per session, 2^31 or more" % (H, W, L))
+        if self._sk_prev is None:
+            self._sk_prev = torch.empty(self.max_streams, L, device=self.dev, dtype=torch.float32)
+            self._sk_hw = (H, W)
+        if (H, W) != self._sk_hw:
+            raise ValueError("StreamPool: frames of %d x %d pushed into a pool whose still= store was made for %d x %d -- a gated pool "
+                             "takes one geometry" % (H, W, self._sk_hw[0], self._sk_hw[1]))
+        states = [self._sk_state[h] for h in handles]
+        rows, f0 = [], 0
+        for s, st, n in zip(recs, states, counts):
+            rows.append([s.slot, f0, n, (s.t - 1) % self.cap if st[0] else -1])
+            f0 += n
+        table = self._sk_tables.upload(rows)
+        flat = frames.view(N, L)
+        need = skhip.workspace_ints(N, L)
+        if self._sk_work is None or self._sk_work.numel() < need:
+            self._sk_work = torch.empty(need, device=self.dev, dtype=torch.int32)
+        changed = torch.empty(N, device=self.dev, dtype=torch.int32)
+        skhip.changed(flat, self._sk_prev, changed, self._sk_work, table, gate.tol)
+        kept, src, runs = plan_still(changed.cpu().tolist(), rows, [st[1] for st in states], gate.limit(L), gate.max_run)
+        NK = len(kept)
+        packing = 0 < NK < N                     # every frame kept: the tower reads `frames`; none kept: there is no tower call
+        packed = torch.empty(NK, L, device=self.dev, dtype=torch.float32) if packing else None
+        skhip.pack(flat, packed, self._sk_prev, self._sk_lists.upload(kept) if packing else skhip.List(None, None, NK), table)
+        for st in states:                        # the store holds this push's frames from here on, the ring their rows once _run is through
+            st[0] = False
+        tower_in = packed.view(NK, 3, H, W) if packing else frames
+        kept_feats = torch.empty(NK, self.E, device=self.dev, dtype=torch.float32) if NK else None
+        for k0 in range(0, NK, eng.max_frames):
+            k1 = min(NK, k0 + eng.max_frames)
+            eng.vit.forward(tower_in[k0:k1], kept_feats[k0:k1])
+        if NK == N:                              # src is 0 .. N - 1: the kept rows are the push's
+            feats = kept_feats
+        else:
+            feats = torch.empty(N, self.E, device=self.dev, dtype=torch.float32)
+            skhip.expand(kept_feats, self._ring, feats, self._sk_lists.upload(src), table)
+        out = self._run(eng, feats, handles, recs, counts)
+        flags = [False] * N
+        for i in kept:
+            flags[i] = True
+        self._sk_last = {}
+        for h, s, st, row, run in zip(handles, recs, states, rows, runs):
+            mine = tuple(flags[row[skhip.F0]:row[skhip.F0] + row[skhip.N]])
+            self._sk_last[h] = mine
+            s.tower_frames += sum(mine)
+            st[0], st[1], st[2] = True, run, st[2] + len(mine) - sum(mine)
+        self._totals["tower_frames"] += NK
+        self._totals["still_frames"] += N - NK
+        return out
+
+    def last_kept(self):
+        """of a pool with still=: {session: a bool per frame of its part of the most recent pixel push -- True: the frame went through
+        the tower}"""
+        if self._still is None:
+            raise ValueError("StreamPool.last_kept: the pool was built without still=")
+        return dict(self._sk_last)
+
     def push_features_packed(self, feats, sessions, counts):
         """feats [N, E] fp32 (device): the tower features of the frames -> as push_packed"""
         eng = self._ready()
         feats, recs, counts = self._check(feats, (self.E,), "feats", "[N, E=%d]" % self.E, sessions, counts)
+        if self._still is not None:              # the sessions' newest frames are no longer the ones in the store
+            for h in sessions:
+                self._sk_state[h][:2] = [False, 0]
         return self._run(eng, feats, list(sessions), recs, counts)
 
     def _by_session(self, packed_call, per_session, what, dims):
