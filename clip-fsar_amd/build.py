@@ -217,10 +217,11 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
 # (clip_fsar_amd.shortlist), the pinned selection of a stream pool with a shortlist, and the OTAM soft alignment behind a score
 # (clip_fsar_amd.align), the tempo windows of a stream pool with rates=, and event evidence (clip_fsar_amd.evidence): an event's
 # window copied out of the ring into a device store by the push that detected it, and the still-frame gate of a stream pool with
-# still= (clip_fsar_amd.still): frames that did not change skip the tower.  ExtLib values again; the open registry.
+# still= (clip_fsar_amd.still): frames that did not change skip the tower, and the contest of a stream pool with contest=
+# (clip_fsar_amd.contest): only a window's leading classes reach the detector.  ExtLib values again; the open registry.
 PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
                             os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
-               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still")}
+               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still", "contest")}
 
 
 def plugin_lib_names() -> list:

@@ -37,6 +37,8 @@
     v.explain_event(e); v.enroll_event(e, "kite")                     # explain / enroll on the kept rows, whatever became of the session
     w = StreamPool(gallery, still=StillGate())                        # clip_fsar_amd.still: frames that repeat their predecessor skip the tower
     w.push({a: frames}); w.last_kept()                                # {a: (True, False, ..)}: which frames went through the tower
+    k = StreamPool(live_gallery, events=EventRule(on=0.6, off=0.4), contest=Contest(top=1))              # clip_fsar_amd.contest
+    k.take_events(); k.leaders(out)                                   # events of a window's best class alone; (columns [nW, top], counts [nW])
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -119,6 +121,14 @@ smoothing, baselines, events, evidence, enrolment and explain see no difference,
 push leave a session without a predecessor: its next frame goes through the tower whatever it holds.  stats() gains "still_frames",
 tower_frames counts the frames the tower really saw, last_kept() tells them apart.  One frame geometry per pool.
 
+contest=Contest(top, margin) (clip_fsar_amd.contest, which states the rule; needs events=): between the judged scores of a push -- after
+smoothing and the baseline -- and the detector, one launch (libclipfsar_contest.so, clip_fsar_amd.contest_hip, over the table and keys the
+detector takes) ranks every window's row: the `top` highest candidates lead, ties to the lower column, and with `margin` none further than
+that below the window's best; every other candidate reaches the detector as -inf.  An idle pair that is demoted loses its streak, a running
+event counts a window below `off` and ends after min_off windows out of the leaders -- with an OFFSET whose score is -inf.  Nothing but the
+detector sees that plane: the push returns the bits it returns without the option (a shortlist pool's pins follow the detector's cells, so an
+outranked pair's pin lapses with its event).  leaders(out) recomputes a push's leading columns on the device.  The stage keeps no state.
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -134,6 +144,7 @@ import torch
 
 from . import baseline_hip as blhip
 from . import class_smooth_hip as cship
+from . import contest_hip as cthip
 from . import enroll_hip as enhip
 from . import evidence_hip as edhip
 from . import events_hip as evhip
@@ -144,6 +155,7 @@ from . import pool_select_hip as pship
 from . import still_hip as skhip
 from . import tempo_hip as tphip
 from .baseline import Baseline
+from .contest import Contest
 from .events import EventRule, translate
 from .evidence import MISSED, Evidence, EvidenceEvent, keep0
 from .gallery import _GalleryBase
@@ -342,8 +354,9 @@ class _Session:
 
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
-                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, events=None, baseline=None):
-        # shortlist=, shortlist_hold=, rates= and evidence= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, contest=None, events=None,
+                 baseline=None):
+        # shortlist=, shortlist_hold=, rates=, evidence=, still= and contest= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
             raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
@@ -390,6 +403,12 @@ class StreamPool:
                                  "pool with events=EventRule(...) as well")
         if still is not None and not isinstance(still, StillGate):
             raise TypeError("StreamPool: still must be a StillGate, got %s" % type(still).__name__)
+        if contest is not None:
+            if not isinstance(contest, Contest):
+                raise TypeError("StreamPool: contest must be a Contest, got %s" % type(contest).__name__)
+            if events is None:
+                raise ValueError("StreamPool: contest= is given without events= -- the contest decides which classes of a window reach "
+                                 "the detector; build the pool with events=EventRule(...) as well")
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
@@ -457,6 +476,10 @@ class StreamPool:
             self._ed_captured = 0                # captures translated so far: the next serial
             # the type of this pool's events: EvidenceEvent under its own name, so that an event says which pool's store holds its window
             self._event_type = type("EvidenceEvent", (EvidenceEvent,), {"__slots__": (), "__doc__": EvidenceEvent.__doc__})
+        self._contest_rule = contest             # the Contest, or None: nothing below is there
+        if contest is not None:
+            self._ct_work = None                 # contest_hip.contest's workspace, grown on demand
+            self._ct_tables = None               # the descriptor tables of leaders(), made by its first call
         self._shortlist = shortlist              # the Shortlist, or None: nothing below is there
         if shortlist is not None:
             self._hold = hold
@@ -886,7 +909,8 @@ class StreamPool:
         if self._baseline is not None:
             judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, judged, cp, after=[s.t for s in recs])     # the counters have moved already
+            seen = judged if self._contest_rule is None else self._contest(cp, judged)     # the detector alone sees the demoted plane
+            self._detect(handles, recs, plan, seen, cp, after=[s.t for s in recs])       # the counters have moved already
         fields = (handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
         return GroupedPackedOutput(*fields) if self._baseline is None else DeviationGroupedPackedOutput(*fields, deviation=deviation)
 
@@ -1025,6 +1049,69 @@ class StreamPool:
         if self._ev_ids[0] != key:
             self._ev_ids = (key, tuple(g.class_ids))
         return self._ev_ids[1]
+
+    def _contest_work(self, n_out):
+        need = cthip.workspace_words(n_out)
+        if self._ct_work is None or self._ct_work.shape[0] < need:
+            self._ct_work = torch.empty(need, device=self.dev, dtype=torch.int32)
+        return self._ct_work
+
+    def _contest(self, cp, judged):
+        """the push's judged plane (dense [NW, C], [NW, K] of a shortlist push, or the grouped layout) -> the plane the detector sees, in
+        the same layout: every window's leaders keep their bits, every other candidate is -inf; one cfct_contest over the table and keys
+        of the push.  Nothing but the detector reads it."""
+        c = self._contest_rule
+        _, gens, keys, table = cp
+        demoted = torch.empty_like(judged)
+        cthip.contest(judged.view(-1), keys, demoted.view(-1), None, None, self._contest_work(judged.numel()), table, gens.shape[0],
+                      c.top, c.margin)
+        return demoted
+
+    def leaders(self, out):
+        """(columns [NW, top] int32, counts [NW] int32) of every window of a push's output, packed or per session: the window's leading
+        classes as the detector saw them, ascending and padded with contest.NONE, and their number.  On the device, no synchronisation.
+        Recomputed from the output's judged plane -- deviation with a baseline, else smoothed with per-class smoothing, else logits --
+        through the pool's own cfct_contest.  A column is an index into gallery.class_ids; of a session with a class list of its own,
+        and of a GroupedPackedOutput, it counts within that session's list; of a shortlist pool's output it is mapped through the
+        session's `columns`, and a place without a class does not compete."""
+        c = self._contest_rule
+        if c is None:
+            raise ValueError("StreamPool.leaders: this pool holds no contest (build it with events=EventRule(...), contest=Contest(...))")
+        judged = getattr(out, "deviation", None)
+        if judged is None:
+            judged = out.logits if out.smoothed is None else out.smoothed
+        keys, cap, lists = None, 1, None
+        if isinstance(out, GroupedPackedOutput):
+            n_windows, widths = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])], list(out.widths)
+        elif hasattr(out, "columns"):              # of a pool with a shortlist: a place competes iff it holds a class
+            K = judged.shape[1]
+            lists = out.columns[None] if out.columns.dim() == 1 else out.columns
+            n_windows = [judged.shape[0]] if out.columns.dim() == 1 else [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])]
+            widths, keys, cap = [K] * len(n_windows), lists.contiguous().view(-1), pship.NONE
+        else:
+            n_windows, widths = [judged.shape[0]], [judged.shape[1]]
+        NW = sum(n_windows)
+        columns = torch.empty(NW, c.top, device=self.dev, dtype=torch.int32)
+        counts = torch.empty(NW, device=self.dev, dtype=torch.int32)
+        if not NW:
+            return columns, counts
+        if not judged.is_cuda:
+            raise RuntimeError("StreamPool.leaders: the output's scores must be a HIP device tensor (no CPU path exists)")
+        rows, n_out = [], 0
+        for i, (nW, NC) in enumerate(zip(n_windows, widths)):
+            rows.append([0, nW, n_out, NC, i * NC if keys is not None else 0, 0])
+            n_out += nW * NC
+        if self._ct_tables is None:
+            self._ct_tables = cship.table_uploader(self.dev, self.max_streams)
+        flat = judged.contiguous().view(-1)
+        cthip.contest(flat, keys, torch.empty_like(flat), columns, counts, self._contest_work(n_out), self._ct_tables.upload(rows), cap,
+                      c.top, c.margin)
+        if lists is not None:                      # places -> indices into gallery.class_ids, as _topk_shortlist maps them
+            group = torch.tensor([i for i, n in enumerate(n_windows) for _ in range(n)], device=self.dev, dtype=torch.int64)
+            found = columns != cthip.NONE
+            place = torch.where(found, columns, torch.zeros_like(columns)).long()
+            columns = torch.where(found, lists[group].gather(1, place), columns)
+        return columns, counts
 
     def _detect(self, handles, recs, plan, scores, cp, columns=None, after=None, tempo=None):
         """one cfev_detect over the push's session-major scores (three launches, no synchronisation); the records stay on the device and
@@ -1277,7 +1364,8 @@ class StreamPool:
         if self._baseline is not None:           # likewise one launch per push, after smoothing and before the detector
             judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
-            self._detect(handles, recs, plan, judged, cp, after=[s.t + n for s, n in zip(recs, counts)], tempo=tempo)
+            seen = judged if self._contest_rule is None else self._contest(cp, judged)     # the detector alone sees the demoted plane
+            self._detect(handles, recs, plan, seen, cp, after=[s.t + n for s, n in zip(recs, counts)], tempo=tempo)
         offsets = [0]
         for s, n, nW in zip(recs, counts, plan.n_windows):
             s.t += n
@@ -1405,8 +1493,10 @@ class StreamPool:
             if self._baseline is not None:
                 judged = deviation = self._normalize(cp, judged)
             if self._events is not None:
+                # (the padded places of a list carry no store slot: they are no candidates of the contest)
+                shown = judged if self._contest_rule is None else self._contest(cp, judged)
                 self._detect([handles[i] for i in live], [recs[i] for i in live], Plan(None, [plan.first_window[i] for i in live], None, None),
-                             judged, cp, columns=sel_cols, after=[recs[i].t + counts[i] for i in live])
+                             shown, cp, columns=sel_cols, after=[recs[i].t + counts[i] for i in live])
             if G == S_push:
                 columns, pinned = sel_cols, sel_pin
             else:
