@@ -171,67 +171,75 @@ GroupedPackedOutput = collections.namedtuple("GroupedPackedOutput", "sessions fi
                                              defaults=(None,))
 
 
-def _with_deviation(base):
-    """the output type of a pool with a baseline: `base`'s tuple, and the attribute `deviation` beside it"""
-    class _Deviating(base):
-        def __new__(cls, *fields, deviation, **more):
-            self = super().__new__(cls, *fields, **more)
-            self.deviation = deviation
-            return self
-    _Deviating.__name__ = _Deviating.__qualname__ = "Deviation" + base.__name__
-    _Deviating.__doc__ = "%s of a pool with a baseline: the same tuple, and .deviation in the layout of .logits (NaN through warm-up)" % base.__name__
-    return _Deviating
+def _class_ids(self):
+    """the class ids behind `columns` (None where a place holds no class), per session of a packed output.  Synchronises."""
+    rows = self.columns.cpu().tolist()
+    name = lambda row: [self._ids[c] if c != pship.NONE else None for c in row]
+    return name(rows) if self.columns.dim() == 1 else [name(row) for row in rows]
 
 
-DeviationPackedOutput = _with_deviation(PackedOutput)
-DeviationGroupedPackedOutput = _with_deviation(GroupedPackedOutput)
-DeviationStreamOutput = _with_deviation(StreamOutput)
+# What an option adds to a push's output: a prefix of the type's name, the keyword-only extras its constructor takes and the instance
+# holds beside the tuple (`ids` as ._ids), the type's docstring and its methods.
+#   Shortlist: logits, smoothed (and deviation) are [nW, K]; columns and pinned are int32 on the device, [K] of a session's output and
+#     [sessions of the push, K] of a packed one; columns: indices into gallery.class_ids as of the push, ascending, NONE where the list
+#     is shorter (every place of a session without windows); pinned: the place's PIN_* bits, 0: selected on its score
+#   Tempo: tempo is int32 on the device in the layout of .logits, per cell the index into `rates`, the pool's tuple, of the tempo
+#     whose score .logits holds
+_EXTRAS = {
+    "Shortlist": (("columns", "pinned", "ids"), "%s of a pool with a shortlist: the same tuple over the K listed classes, .columns, "
+                  ".pinned and .class_ids()", {"class_ids": _class_ids}),
+    "Tempo": (("tempo", "rates"), "%s of a pool with rates=: the same tuple, .tempo in the layout of .logits and .rates", {}),
+    "Deviation": (("deviation",), "%s of a pool with a baseline: the same tuple, and .deviation in the layout of .logits (NaN through "
+                  "warm-up)", {}),
+}
+_OUTPUT_TYPES = {t.__name__: t for t in (PackedOutput, GroupedPackedOutput, StreamOutput)}
 
 
-def _with_columns(base):
-    """the output type of a pool with a shortlist: `base`'s tuple -- logits, smoothed (and deviation) are [nW, K] -- and beside it
-    `columns` and `pinned`: int32 on the device, [K] of a session's output and [sessions of the push, K] of a packed one; columns: indices
-    into gallery.class_ids as of the push, ascending, NONE where the list is shorter (every place of a session without windows);
-    pinned: the place's PIN_* bits, 0: selected on its score"""
-    class _Listed(base):
-        def __new__(cls, *fields, columns, pinned, ids):
-            self = super().__new__(cls, *fields)
-            self.columns, self.pinned, self._ids = columns, pinned, ids
-            return self
+def _extended(prefix, base):
+    """the output type `prefix` + `base`'s name: a subclass of `base` with the same tuple whose constructor takes the option's extras by
+    keyword and hands every other keyword on to `base`"""
+    extras, doc, methods = _EXTRAS[prefix]
 
-        def class_ids(self):
-            """the class ids behind `columns` (None where a place holds no class), per session of a packed output.  Synchronises."""
-            rows = self.columns.cpu().tolist()
-            name = lambda row: [self._ids[c] if c != pship.NONE else None for c in row]
-            return name(rows) if self.columns.dim() == 1 else [name(row) for row in rows]
-    _Listed.__name__ = _Listed.__qualname__ = "Shortlist" + base.__name__
-    _Listed.__doc__ = "%s of a pool with a shortlist: the same tuple over the K listed classes, .columns, .pinned and .class_ids()" % base.__name__
-    return _Listed
+    def __new__(cls, *fields, **more):
+        missing = [k for k in extras if k not in more]
+        if missing:
+            raise TypeError("%s() needs the keyword-only arguments %s" % (cls.__name__, ", ".join(missing)))
+        mine = [more.pop(k) for k in extras]
+        self = base.__new__(cls, *fields, **more)
+        for k, v in zip(extras, mine):
+            setattr(self, "_ids" if k == "ids" else k, v)
+        return self
+    t = type(prefix + base.__name__, (base,), dict(methods, __new__=__new__, __doc__=doc % base.__name__, __module__=__name__))
+    _OUTPUT_TYPES[t.__name__] = t
+    return t
 
 
-ShortlistPackedOutput = _with_columns(PackedOutput)
-ShortlistStreamOutput = _with_columns(StreamOutput)
-DeviationShortlistPackedOutput = _with_deviation(ShortlistPackedOutput)
-DeviationShortlistStreamOutput = _with_deviation(ShortlistStreamOutput)
+DeviationPackedOutput = _extended("Deviation", PackedOutput)
+DeviationGroupedPackedOutput = _extended("Deviation", GroupedPackedOutput)
+DeviationStreamOutput = _extended("Deviation", StreamOutput)
+ShortlistPackedOutput = _extended("Shortlist", PackedOutput)
+ShortlistStreamOutput = _extended("Shortlist", StreamOutput)
+DeviationShortlistPackedOutput = _extended("Deviation", ShortlistPackedOutput)
+DeviationShortlistStreamOutput = _extended("Deviation", ShortlistStreamOutput)
+TempoPackedOutput = _extended("Tempo", PackedOutput)
+TempoStreamOutput = _extended("Tempo", StreamOutput)
+DeviationTempoPackedOutput = _extended("Deviation", TempoPackedOutput)
+DeviationTempoStreamOutput = _extended("Deviation", TempoStreamOutput)
 
 
-def _with_tempo(base):
-    """the output type of a pool with rates=: `base`'s tuple, and beside it `tempo` -- int32 on the device in the layout of .logits, per
-    cell the index into `rates` of the tempo whose score .logits holds -- and `rates`, the pool's tuple"""
-    class _Tempo(base):
-        def __new__(cls, *fields, tempo, rates):
-            self = super().__new__(cls, *fields)
-            self.tempo, self.rates = tempo, rates
-            return self
-    _Tempo.__name__ = _Tempo.__qualname__ = "Tempo" + base.__name__
-    _Tempo.__doc__ = "%s of a pool with rates=: the same tuple, .tempo in the layout of .logits and .rates" % base.__name__
-    return _Tempo
+def _output(base, *fields, deviation=None, tempo=None, rates=None, columns=None, pinned=None, ids=None):
+    """the output of a push or of one of its sessions: `base` (PackedOutput, GroupedPackedOutput or StreamOutput) over `fields` when no
+    extra is given, else the subclass the extras present name, holding them"""
+    name, more = base.__name__, {}
+    if columns is not None:
+        name, more = "Shortlist" + name, dict(columns=columns, pinned=pinned, ids=ids)
+    if tempo is not None:
+        name, more = "Tempo" + name, dict(tempo=tempo, rates=rates)
+    if deviation is not None:
+        name, more = "Deviation" + name, dict(more, deviation=deviation)
+    return _OUTPUT_TYPES[name](*fields, **more)
 
 
-TempoPackedOutput = _with_tempo(PackedOutput)
-TempoStreamOutput = _with_tempo(StreamOutput)
-DeviationTempoPackedOutput = _with_deviation(TempoPackedOutput)
-DeviationTempoStreamOutput = _with_deviation(TempoStreamOutput)
 # One round of a push.  rows: the descriptor table, a row per session that still has frames (pool_hip's column order); members: the
 # position of each row's session in the push; src: (first row, n) of each row's frames in the push's packed frames.
 Round = collections.namedtuple("Round", "rows members src")
@@ -352,6 +360,42 @@ class _Session:
         self.state_layout = None                 # the gallery's layout_version then (None: a gallery whose columns never change meaning)
 
 
+class _Cells:
+    """A keyed cell store: planes [max_streams, store capacity], a cell per (session slot, class store slot), made by the first push
+    that needs them.  dtypes: a plane each; guard: the indices of the planes that say whether a cell holds anything -- the generation
+    marks, or a shortlist's two clocks -- which are made zero-filled and whose rows of the slots in `forgotten` (sessions opened or
+    reset since the last push) are zeroed by the next push; the other planes are read behind a guard alone and are made uninitialised."""
+
+    def __init__(self, dev, max_streams, dtypes, guard, limit, what):
+        self.dev, self.max_streams, self.dtypes, self.guard, self.limit, self.what = dev, max_streams, dtypes, guard, limit, what
+        self.planes = None
+        self.forgotten = set()
+
+    @staticmethod
+    def too_many(max_streams, cap, what):
+        return ("StreamPool: %s keeps a state cell per (session slot, store slot): max_streams = %d x store capacity = %d "
+                "is 2^31 or more -- build the pool with fewer streams or the gallery with fewer slots" % (what, max_streams, cap))
+
+    def at(self, cap):
+        """the planes at store capacity `cap`; a grown store: reallocated with their columns copied, the guards' new columns 0.  The
+        forgotten slots' rows of the guards are zeroed here, on the push's stream."""
+        if self.max_streams * cap > self.limit:
+            raise ValueError(self.too_many(self.max_streams, cap, self.what))
+        old = None if self.planes is None else self.planes[0].shape[1]
+        if old != cap:
+            new = tuple((torch.zeros if i in self.guard else torch.empty)(self.max_streams, cap, device=self.dev, dtype=dtype)
+                        for i, dtype in enumerate(self.dtypes))
+            if old is not None:
+                for t, was in zip(new, self.planes):
+                    t[:, :old].copy_(was)
+            self.planes = new
+        for slot in sorted(self.forgotten):
+            for i in self.guard:
+                self.planes[i][slot].zero_()
+        self.forgotten.clear()
+        return self.planes
+
+
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
                  *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, contest=None, events=None,
@@ -383,18 +427,23 @@ class StreamPool:
             raise ValueError("StreamPool: smooth_by=\"class\" needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
                              % type(gallery).__name__)
         if smooth_by == "class" and smooth and max_streams * gallery.capacity > cship.MAX_CELLS:
-            raise ValueError(self._too_many_cells(max_streams, gallery.capacity))
+            raise ValueError(_Cells.too_many(max_streams, gallery.capacity, "smooth_by=\"class\""))
+
+        def keyed(what, why, limit, slot_store=True):
+            """what an option that keeps a cell per (session slot, store slot) asks of the pool: `what` names the option, `why` says
+            what its state is keyed by, `limit` is its library's MAX_CELLS"""
+            if slot_store and not hasattr(gallery, "slot_generations"):
+                raise ValueError("StreamPool: %s needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
+                                 % (what, type(gallery).__name__))
+            if smooth and smooth_by == "column":
+                raise ValueError("StreamPool: %s on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
+                                 "keyed by column, %s" % (what, why))
+            if max_streams * gallery.capacity > limit:
+                raise ValueError(_Cells.too_many(max_streams, gallery.capacity, what))
         if events is not None:
             if not isinstance(events, EventRule):
                 raise TypeError("StreamPool: events must be an EventRule, got %s" % type(events).__name__)
-            if not hasattr(gallery, "slot_generations"):
-                raise ValueError("StreamPool: events= needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
-                                 % type(gallery).__name__)
-            if smooth and smooth_by == "column":
-                raise ValueError("StreamPool: events= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
-                                 "keyed by column, the detector's by class")
-            if max_streams * gallery.capacity > evhip.MAX_CELLS:
-                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "events="))
+            keyed("events=", "the detector's by class", evhip.MAX_CELLS)
         if evidence is not None:
             if not isinstance(evidence, Evidence):
                 raise TypeError("StreamPool: evidence must be an Evidence, got %s" % type(evidence).__name__)
@@ -412,14 +461,7 @@ class StreamPool:
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
-            if not hasattr(gallery, "slot_generations"):
-                raise ValueError("StreamPool: baseline= needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
-                                 % type(gallery).__name__)
-            if smooth and smooth_by == "column":
-                raise ValueError("StreamPool: baseline= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
-                                 "keyed by column, the baseline's by class")
-            if max_streams * gallery.capacity > blhip.MAX_CELLS:
-                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "baseline="))
+            keyed("baseline=", "the baseline's by class", blhip.MAX_CELLS)
         if shortlist is None and shortlist_hold is not None:
             raise ValueError("StreamPool: shortlist_hold = %r is given without shortlist= -- there is no list to hold a class in"
                              % (shortlist_hold,))
@@ -429,14 +471,10 @@ class StreamPool:
                 raise TypeError("StreamPool: shortlist must be a Shortlist, got %s" % type(shortlist).__name__)
             if shortlist.gallery is not gallery:
                 raise ValueError("StreamPool: shortlist= was built over another gallery -- shortlist.gallery must be the pool's gallery")
-            if smooth and smooth_by == "column":
-                raise ValueError("StreamPool: shortlist= on a pool with smooth > 0 needs smooth_by=\"class\" -- the column mode's state is "
-                                 "keyed by column, and a shortlist's columns change with every push")
+            keyed("shortlist=", "and a shortlist's columns change with every push", pship.MAX_CELLS, slot_store=False)
             hold = 0 if shortlist_hold is None else shortlist_hold
             if isinstance(hold, bool) or not isinstance(hold, int) or not 0 <= hold <= pship.MAX_HOLD:
                 raise ValueError("StreamPool: shortlist_hold must be an integer in [0, 2^20], got %r" % (shortlist_hold,))
-            if max_streams * gallery.capacity > pship.MAX_CELLS:
-                raise ValueError(self._too_many_cells(max_streams, gallery.capacity, "shortlist="))
         self.smooth_by = smooth_by
         self._by_class = smooth_by == "class" and bool(smooth)     # with smooth = 0 the option is inert
         self.gallery = gallery
@@ -447,10 +485,16 @@ class StreamPool:
         self.cap = (self.T - 1) * rate + max_push
         self._ring = torch.empty(max_streams, self.cap, self.E, device=self.dev, dtype=torch.float32)
         self._X = None                           # gathered windows [rows, T, E], grown on demand
-        self._state = None                       # smoothing state [max_streams, C], indexed by slot
+        self._state = None                       # the column mode's smoothing state [max_streams, C], indexed by slot
         self._state_gen = 0                      # bumped whenever _state is allocated anew (the class count changed)
-        self._marks = None                       # smooth_by="class": _state is [max_streams, store capacity] by (slot, store slot), and
-        self._unmarked = set()                   # _marks the generations beside it; the slots whose row of marks is to be zeroed
+        self._stores = []                        # the keyed cell stores of the options given; open() and reset() walk them
+        i32, f32 = torch.int32, torch.float32
+
+        def cells(dtypes, guard, limit, what):
+            self._stores.append(_Cells(self.dev, max_streams, dtypes, guard, limit, what))
+            return self._stores[-1]
+        # smooth_by="class": (state, marks) by (slot, store slot), the marks the generations beside the state; None: nothing is kept
+        self._smooth_cells = cells((f32, i32), (1,), cship.MAX_CELLS, "smooth_by=\"class\"") if self._by_class else None
         self._smooth_tables = None               # class_smooth_hip's descriptor tables, made by the first class-mode push
         self._smooth_keys = (None, None, None)   # the last push's own store-slot lists, the gallery's column list then, their device form
         self._tables = php.TableUploader(self.dev, max_streams)
@@ -462,8 +506,7 @@ class StreamPool:
         self._events = events                    # the EventRule, or None: nothing below is there
         if events is not None:
             self._totals.update(events=0, events_dropped=0)
-            self._ev_cells = None                # (streak, length, peak, marks), each [max_streams, store capacity]
-            self._ev_unmarked = set()            # the slots whose row of the detector's marks is to be zeroed, as _unmarked
+            self._ev_cells = cells((i32, i32, f32, i32), (3,), evhip.MAX_CELLS, "events=")       # (streak, length, peak, marks)
             self._ev_work = None                 # events_hip.detect's workspace, grown on demand
             self._ev_queue = collections.deque() # EventBatch per push that ran the detector, oldest first
             self._ev_ready = []                  # Events of batches a push had to translate itself
@@ -484,15 +527,13 @@ class StreamPool:
         if shortlist is not None:
             self._hold = hold
             self._totals.update(pins=0, pins_dropped=0)
-            self._sl_planes = None               # (seen, merit), each [max_streams, store capacity] int32
-            self._sl_unmarked = set()            # the slots whose rows of both planes are to be zeroed, as _unmarked
+            self._sl_cells = cells((i32, i32), (0, 1), pship.MAX_CELLS, "shortlist=")            # (seen, merit), both their own guard
             self._sl_tables = None               # pool_select_hip's group tables, made by the first scoring push
             self._sl_pins = None                 # [2] int64 on the device: pins and dropped pins of the pushes not yet read
             self._ev_ids = (None, None)          # _every_class_ids' cache, with or without a rule: the ids behind a push's columns
         self._baseline = baseline                # the Baseline, or None: nothing below is there
         if baseline is not None:
-            self._bl_cells = None                # (mean, dev, count, marks), each [max_streams, store capacity]
-            self._bl_unmarked = set()            # the slots whose row of the baselines' marks is to be zeroed, as _unmarked
+            self._bl_cells = cells((f32, f32, i32, i32), (3,), blhip.MAX_CELLS, "baseline=")     # (mean, dev, count, marks)
         self._still = still                      # the StillGate, or None: nothing below is there
         if still is not None:
             self._totals.update(still_frames=0)
@@ -559,17 +600,15 @@ class StreamPool:
         h = self._next_handle
         self._next_handle += 1
         self._sessions[h] = _Session(heapq.heappop(self._free), classes)
-        if self._still is not None:
-            self._sk_state[h] = [False, 0, 0]    # no predecessor: the frame a previous owner of the slot left in the store is never read
-        if self._by_class:
-            self._unmarked.add(self._sessions[h].slot)      # nothing of the slot's previous owner is read
-        if self._events is not None:
-            self._ev_unmarked.add(self._sessions[h].slot)
-        if self._baseline is not None:
-            self._bl_unmarked.add(self._sessions[h].slot)
-        if self._shortlist is not None:
-            self._sl_unmarked.add(self._sessions[h].slot)
+        self._forget(h, self._sessions[h])       # nothing of the slot's previous owner is read
         return h
+
+    def _forget(self, h, s):
+        """the session starts anew: no predecessor frame, and every store zeroes the slot's guards at the next push"""
+        if self._still is not None:
+            self._sk_state[h] = [False, 0, 0]    # the frame a previous owner of the slot left in the store is never read
+        for store in self._stores:
+            store.forgotten.add(s.slot)
 
     def _session_lists(self, handles, lists):
         """the sessions' class lists under the gallery's rules (registered, no repeats, not empty); an error names the session"""
@@ -595,16 +634,7 @@ class StreamPool:
         """Frame counter 0; the session's ring contents and smoothing state are dropped."""
         s = self._session(h)
         s.clear()
-        if self._still is not None:
-            self._sk_state[h] = [False, 0, 0]
-        if self._by_class:
-            self._unmarked.add(s.slot)
-        if self._events is not None:
-            self._ev_unmarked.add(s.slot)
-        if self._baseline is not None:
-            self._bl_unmarked.add(s.slot)
-        if self._shortlist is not None:
-            self._sl_unmarked.add(s.slot)
+        self._forget(h, s)
 
     @property
     def sessions(self):
@@ -713,11 +743,9 @@ class StreamPool:
             f0 += n
         table = self._sk_tables.upload(rows)
         flat = frames.view(N, L)
-        need = skhip.workspace_ints(N, L)
-        if self._sk_work is None or self._sk_work.numel() < need:
-            self._sk_work = torch.empty(need, device=self.dev, dtype=torch.int32)
+        work = self._work("_sk_work", skhip.workspace_ints(N, L))
         changed = torch.empty(N, device=self.dev, dtype=torch.int32)
-        skhip.changed(flat, self._sk_prev, changed, self._sk_work, table, gate.tol)
+        skhip.changed(flat, self._sk_prev, changed, work, table, gate.tol)
         kept, src, runs = plan_still(changed.cpu().tolist(), rows, [st[1] for st in states], gate.limit(L), gate.max_run)
         NK = len(kept)
         packing = 0 < NK < N                     # every frame kept: the tower reads `frames`; none kept: there is no tower call
@@ -783,26 +811,18 @@ class StreamPool:
     def _split(po):
         """PackedOutput or GroupedPackedOutput -> {session: StreamOutput}"""
         out = {}
-        deviation = getattr(po, "deviation", None)      # of a pool with a baseline: each session's StreamOutput carries its block too
-        tempo = getattr(po, "tempo", None)              # of a pool with rates=: likewise its block of the tempo plane
+        planes = [(k, getattr(po, k, None)) for k in ("smoothed", "deviation", "tempo")]     # each session carries its block of them
+        rows = [(k, getattr(po, k, None)) for k in ("columns", "pinned")]                    # and its row of a shortlist's lists
         for i, h in enumerate(po.sessions):
             w0, w1 = po.offsets[i], po.offsets[i + 1]
             if isinstance(po, GroupedPackedOutput):
                 block = lambda t: t[po.logit_offsets[i]:po.logit_offsets[i + 1]].view(w1 - w0, po.widths[i])
             else:
                 block = lambda t: t[w0:w1]
-            fields = (po.first_window[i], block(po.logits), None if po.smoothed is None else block(po.smoothed))
-            if hasattr(po, "columns"):              # of a pool with a shortlist: the session's row of the lists
-                more = dict(columns=po.columns[i], pinned=po.pinned[i], ids=po._ids)
-                out[h] = (ShortlistStreamOutput(*fields, **more) if deviation is None
-                          else DeviationShortlistStreamOutput(*fields, deviation=block(deviation), **more))
-                continue
-            if tempo is not None:
-                more = dict(tempo=block(tempo), rates=po.rates)
-                out[h] = (TempoStreamOutput(*fields, **more) if deviation is None
-                          else DeviationTempoStreamOutput(*fields, deviation=block(deviation), **more))
-                continue
-            out[h] = StreamOutput(*fields) if deviation is None else DeviationStreamOutput(*fields, deviation=block(deviation))
+            mine = {k: None if t is None else block(t) for k, t in planes}
+            mine.update((k, None if t is None else t[i]) for k, t in rows)
+            out[h] = _output(StreamOutput, po.first_window[i], block(po.logits), mine.pop("smoothed"), rates=getattr(po, "rates", None),
+                             ids=getattr(po, "_ids", None), **mine)
         return out
 
     def push(self, frames):
@@ -899,43 +919,33 @@ class StreamPool:
                 at = logit_offsets[i] + done[i] * widths[i]
                 logits[at:at + n * widths[i]].copy_(res.logits[res.offsets[j]:res.offsets[j + 1]])
                 done[i] += n
-        for s, n in zip(recs, counts):
-            s.t += n
-        self._totals["frames"] += sum(counts)
-        self._totals["windows"] += offsets[-1]
         cp = self._class_push(recs, plan.n_windows) if self._keyed and logits.numel() else None
-        smoothed = self._smooth_classes(cp, logits) if self._by_class else None
-        judged = smoothed if self._by_class else logits
+        smoothed, deviation = self._judge(logits, cp, handles, recs, counts, plan.first_window)
+        self._advance(recs, counts, offsets[-1])
+        return _output(GroupedPackedOutput, handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed, deviation=deviation)
+
+    def _judge(self, logits, cp, handles, recs, counts, first_window, columns=None, tempo=None):
+        """what follows scoring in every push, over its session-major logits (dense [NW, C], [NW, K] of a shortlist push, or the grouped
+        layout): per-class smoothing, the baseline, the contest and the detector, one after the other over the same table and keys ->
+        (smoothed, deviation), each None without its option.  cp: _class_push's, None when the push completed no window or no option
+        keeps cells; handles, recs, counts, first_window: of the table's rows -- the sessions of the push, of a shortlist push (which
+        passes its `columns`) those with windows; their frame counters have not moved yet.  tempo: the push's tempo plane."""
+        smoothed = self._smooth_classes(cp, logits) if self._by_class else None       # one launch, on the session-major logits: a
+        judged = smoothed if self._by_class else logits                               # session's rounds stay in sequence
+        deviation = None
         if self._baseline is not None:
             judged = deviation = self._normalize(cp, judged)
         if cp is not None and self._events is not None:
             seen = judged if self._contest_rule is None else self._contest(cp, judged)     # the detector alone sees the demoted plane
-            self._detect(handles, recs, plan, seen, cp, after=[s.t for s in recs])       # the counters have moved already
-        fields = (handles, plan.first_window, offsets, logits, logit_offsets, widths, smoothed)
-        return GroupedPackedOutput(*fields) if self._baseline is None else DeviationGroupedPackedOutput(*fields, deviation=deviation)
+            self._detect(handles, recs, first_window, seen, cp, columns, [s.t + n for s, n in zip(recs, counts)], tempo)
+        return smoothed, deviation
 
-    @staticmethod
-    def _too_many_cells(max_streams, cap, what="smooth_by=\"class\""):
-        return ("StreamPool: %s keeps a state cell per (session slot, store slot): max_streams = %d x store capacity = %d "
-                "is 2^31 or more -- build the pool with fewer streams or the gallery with fewer slots" % (what, max_streams, cap))
-
-    def _class_state(self, cap):
-        """state and marks [max_streams, cap]; a grown store: reallocated with their columns copied, the marks' new columns invalid.  The
-        rows of marks of sessions opened or reset since the last push are zeroed here, on the push's stream."""
-        if self.max_streams * cap > cship.MAX_CELLS:
-            raise ValueError(self._too_many_cells(self.max_streams, cap))
-        old = None if self._state is None else self._state.shape[1]
-        if old != cap:
-            state = torch.empty(self.max_streams, cap, device=self.dev, dtype=torch.float32)
-            marks = torch.zeros(self.max_streams, cap, device=self.dev, dtype=torch.int32)
-            if old is not None:
-                state[:, :old].copy_(self._state)
-                marks[:, :old].copy_(self._marks)
-            self._state, self._marks = state, marks
-        for slot in sorted(self._unmarked):
-            self._marks[slot].zero_()
-        self._unmarked.clear()
-        return self._state, self._marks
+    def _advance(self, recs, counts, NW):
+        """the push is enqueued: its sessions' frame counters and the pool's totals move"""
+        for s, n in zip(recs, counts):
+            s.t += n
+        self._totals["frames"] += sum(counts)
+        self._totals["windows"] += NW
 
     def _class_push(self, recs, n_windows):
         """what the launches over (session slot, store slot) cells share in one push -- per-class smoothing and the event detector: the
@@ -963,7 +973,7 @@ class StreamPool:
         if cp is None:
             return smoothed
         _, gens, keys, table = cp
-        state, marks = self._class_state(gens.shape[0])
+        state, marks = self._smooth_cells.at(gens.shape[0])
         cship.smooth_classes(logits.view(-1), state, marks, gens, keys, smoothed.view(-1), table, self.alpha)
         return smoothed
 
@@ -973,25 +983,6 @@ class StreamPool:
         """whether a push runs a launch over (session slot, store slot) cells, i.e. needs _class_push's plan and upload"""
         return self._by_class or self._events is not None or self._baseline is not None
 
-    def _baseline_cells(self, cap):
-        """the baselines' cells (mean, dev, count, marks), each [max_streams, cap], grown with the store as _class_state grows its own:
-        the columns copied, the marks' new columns invalid; the rows of marks of sessions opened or reset since the last push are zeroed
-        here, on the push's stream"""
-        if self.max_streams * cap > blhip.MAX_CELLS:
-            raise ValueError(self._too_many_cells(self.max_streams, cap, "baseline="))
-        old = None if self._bl_cells is None else self._bl_cells[0].shape[1]
-        if old != cap:
-            new = tuple((torch.zeros if i == 3 else torch.empty)(self.max_streams, cap, device=self.dev,
-                                                                 dtype=torch.float32 if i < 2 else torch.int32) for i in range(4))
-            if old is not None:
-                for t, was in zip(new, self._bl_cells):
-                    t[:, :old].copy_(was)
-            self._bl_cells = new
-        for slot in sorted(self._bl_unmarked):
-            self._bl_cells[3][slot].zero_()
-        self._bl_unmarked.clear()
-        return self._bl_cells
-
     def _normalize(self, cp, scores):
         """the push's session-major scores (dense [NW, C] or the grouped layout) -> their deviations in the same layout; one
         cfbl_normalize over every session of the push.  cp: _class_push's, None when the push completed no window"""
@@ -1000,7 +991,7 @@ class StreamPool:
             return deviation
         b = self._baseline
         _, gens, keys, table = cp
-        cells = self._baseline_cells(gens.shape[0])
+        cells = self._bl_cells.at(gens.shape[0])
         blhip.normalize(scores.view(-1), *cells, gens, keys, deviation.view(-1), table, b.rate, b.warm_rate, b.warmup, b.gate, b.floor)
         return deviation
 
@@ -1010,39 +1001,28 @@ class StreamPool:
         if self._baseline is None:
             raise ValueError("StreamPool.baseline: this pool keeps no baselines (build it with baseline=Baseline(...))")
         s = self._session(h)
-        if self._bl_cells is None or s.slot in self._bl_unmarked:
+        ids, at, valid = self._live_cells(s, self._bl_cells)
+        if not ids:
             return []
-        mean, dev, count, marks = self._bl_cells
+        cols = [t[s.slot].index_select(0, at).tolist() for t in self._bl_cells.planes[:3]]
+        return [(c, m, d, n) for c, live, m, d, n in zip(ids, valid.tolist(), *cols) if live]
+
+    def _live_cells(self, s, store):
+        """of a store whose last plane holds the generation marks: (the session's class ids that have a cell, in the order of its
+        columns; their store slots `at`, a device index; whether each cell's mark is the slot's current generation and, of a pool with a
+        shortlist, the pair was scored at the session's last scoring push) -- ([], None, None) when there is none"""
+        if store.planes is None or s.slot in store.forgotten:
+            return [], None, None
+        marks = store.planes[-1]
         book = self.gallery._book
         ids = [c for c in (book.order if s.classes is None else s.classes) if c in book.slot_of and book.slot_of[c] < marks.shape[1]]
         if not ids:
-            return []
+            return [], None, None
         at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
         gens = self.gallery.slot_generations().index_select(0, at)
-        valid = ((marks[s.slot].index_select(0, at) == gens) & self._listed(s, at)).tolist()
-        cols = [t[s.slot].index_select(0, at).tolist() for t in (mean, dev, count)]
-        return [(c, m, d, n) for c, live, m, d, n in zip(ids, valid, *cols) if live]
+        return ids, at, (marks[s.slot].index_select(0, at) == gens) & self._listed(s, at)
 
     # ------------------------------------------------------------------ events
-    def _event_cells(self, cap):
-        """the detector's cells (streak, length, peak, marks), each [max_streams, cap], grown with the store as _class_state grows its
-        own: the columns copied, the marks' new columns invalid; the rows of marks of sessions opened or reset since the last push are
-        zeroed here, on the push's stream"""
-        if self.max_streams * cap > evhip.MAX_CELLS:
-            raise ValueError(self._too_many_cells(self.max_streams, cap, "events="))
-        old = None if self._ev_cells is None else self._ev_cells[0].shape[1]
-        if old != cap:
-            new = tuple((torch.zeros if i == 3 else torch.empty)(self.max_streams, cap, device=self.dev,
-                                                                 dtype=torch.float32 if i == 2 else torch.int32) for i in range(4))
-            if old is not None:
-                for t, was in zip(new, self._ev_cells):
-                    t[:, :old].copy_(was)
-            self._ev_cells = new
-        for slot in sorted(self._ev_unmarked):
-            self._ev_cells[3][slot].zero_()
-        self._ev_unmarked.clear()
-        return self._ev_cells
-
     def _every_class_ids(self):
         g = self.gallery
         key = (g.layout_version, len(g))          # columns change their meaning with a removal and are appended by an addition
@@ -1050,11 +1030,13 @@ class StreamPool:
             self._ev_ids = (key, tuple(g.class_ids))
         return self._ev_ids[1]
 
-    def _contest_work(self, n_out):
-        need = cthip.workspace_words(n_out)
-        if self._ct_work is None or self._ct_work.shape[0] < need:
-            self._ct_work = torch.empty(need, device=self.dev, dtype=torch.int32)
-        return self._ct_work
+    def _work(self, name, need):
+        """the int32 workspace kept under the attribute `name`, grown on demand to `need` elements"""
+        work = getattr(self, name)
+        if work is None or work.numel() < need:
+            work = torch.empty(need, device=self.dev, dtype=torch.int32)
+            setattr(self, name, work)
+        return work
 
     def _contest(self, cp, judged):
         """the push's judged plane (dense [NW, C], [NW, K] of a shortlist push, or the grouped layout) -> the plane the detector sees, in
@@ -1063,8 +1045,8 @@ class StreamPool:
         c = self._contest_rule
         _, gens, keys, table = cp
         demoted = torch.empty_like(judged)
-        cthip.contest(judged.view(-1), keys, demoted.view(-1), None, None, self._contest_work(judged.numel()), table, gens.shape[0],
-                      c.top, c.margin)
+        work = self._work("_ct_work", cthip.workspace_words(judged.numel()))
+        cthip.contest(judged.view(-1), keys, demoted.view(-1), None, None, work, table, gens.shape[0], c.top, c.margin)
         return demoted
 
     def leaders(self, out):
@@ -1084,10 +1066,8 @@ class StreamPool:
         if isinstance(out, GroupedPackedOutput):
             n_windows, widths = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])], list(out.widths)
         elif hasattr(out, "columns"):              # of a pool with a shortlist: a place competes iff it holds a class
-            K = judged.shape[1]
-            lists = out.columns[None] if out.columns.dim() == 1 else out.columns
-            n_windows = [judged.shape[0]] if out.columns.dim() == 1 else [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])]
-            widths, keys, cap = [K] * len(n_windows), lists.contiguous().view(-1), pship.NONE
+            n_windows, lists = self._shortlist_groups(out)
+            widths, keys, cap = [judged.shape[1]] * len(n_windows), lists.contiguous().view(-1), pship.NONE
         else:
             n_windows, widths = [judged.shape[0]], [judged.shape[1]]
         NW = sum(n_windows)
@@ -1104,34 +1084,42 @@ class StreamPool:
         if self._ct_tables is None:
             self._ct_tables = cship.table_uploader(self.dev, self.max_streams)
         flat = judged.contiguous().view(-1)
-        cthip.contest(flat, keys, torch.empty_like(flat), columns, counts, self._contest_work(n_out), self._ct_tables.upload(rows), cap,
-                      c.top, c.margin)
-        if lists is not None:                      # places -> indices into gallery.class_ids, as _topk_shortlist maps them
-            group = torch.tensor([i for i, n in enumerate(n_windows) for _ in range(n)], device=self.dev, dtype=torch.int64)
-            found = columns != cthip.NONE
-            place = torch.where(found, columns, torch.zeros_like(columns)).long()
-            columns = torch.where(found, lists[group].gather(1, place), columns)
-        return columns, counts
+        work = self._work("_ct_work", cthip.workspace_words(n_out))
+        cthip.contest(flat, keys, torch.empty_like(flat), columns, counts, work, self._ct_tables.upload(rows), cap, c.top, c.margin)
+        return columns if lists is None else self._listed_classes(columns, cthip.NONE, n_windows, lists), counts
 
-    def _detect(self, handles, recs, plan, scores, cp, columns=None, after=None, tempo=None):
+    @staticmethod
+    def _shortlist_groups(out):
+        """a shortlist pool's output -> (the windows of each of its groups, their lists [groups, K]): a session's output is one group,
+        a packed output holds one per session"""
+        if out.columns.dim() == 1:
+            return [out.logits.shape[0]], out.columns[None]
+        return [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])], out.columns
+
+    def _listed_classes(self, places, none, n_windows, lists):
+        """places [NW, k] int32 into the K places of each window's group (`none`: no place) -> the indices into gallery.class_ids that
+        the group's list holds there; `none` stays"""
+        group = torch.tensor([i for i, n in enumerate(n_windows) for _ in range(n)], device=self.dev, dtype=torch.int64)
+        found = places != none
+        place = torch.where(found, places, torch.zeros_like(places)).long()
+        return torch.where(found, lists[group].gather(1, place), places)
+
+    def _detect(self, handles, recs, first_window, scores, cp, columns=None, after=None, tempo=None):
         """one cfev_detect over the push's session-major scores (three launches, no synchronisation); the records stay on the device and
-        are queued with the push's metadata.  columns: of a shortlist push, its sel_cols -- handles, recs and plan.first_window then hold
+        are queued with the push's metadata.  columns: of a shortlist push, its sel_cols -- handles, recs and first_window then hold
         the sessions with windows alone, the table's rows.  after, tempo (a pool with evidence=): the frames each session will have
         after this push and the push's tempo plane -- the capture follows the detector on the same stream."""
         rule = self._events
         cplan, gens, keys, table = cp
-        cells = self._event_cells(gens.shape[0])
-        need = evhip.workspace_ints(cplan.n_chunks)
-        if self._ev_work is None or self._ev_work.shape[0] < need:
-            self._ev_work = torch.empty(need, device=self.dev, dtype=torch.int32)
+        cells = self._ev_cells.at(gens.shape[0])
         M = rule.max_events
         n_where = 0 if self._evidence is None else 2 * M      # the capture's `where` rides behind the records: one copy brings both down
         buf = torch.empty(1 + (evhip.EVENT_COLS + evhip.VALUE_COLS) * M + n_where, device=self.dev, dtype=torch.int32)
         events, values = self._records(buf, M)
-        evhip.detect(scores.view(-1), *cells, gens, keys, events, values, buf[:1], self._ev_work, table, rule.on, rule.off, rule.min_on,
-                     rule.min_off)
+        work = self._work("_ev_work", evhip.workspace_ints(cplan.n_chunks))
+        evhip.detect(scores.view(-1), *cells, gens, keys, events, values, buf[:1], work, table, rule.on, rule.off, rule.min_on, rule.min_off)
         if self._evidence is not None:
-            self._capture(plan.first_window, cplan.rows, after, events, buf[:1], self._where(buf, M), tempo)
+            self._capture(first_window, cplan.rows, after, events, buf[:1], self._where(buf, M), tempo)
         if len(self._ev_queue) >= EVENT_QUEUE:     # a full queue: the oldest batch is translated here and kept for take_events()
             self._ev_ready.extend(self._translate([self._ev_queue.popleft()]))
         every = None
@@ -1140,7 +1128,7 @@ class StreamPool:
             if s.classes is None:
                 every = self._every_class_ids() if every is None else every
             ids.append(every if s.classes is None else s.classes)       # a session's list is replaced (enroll's join), never changed
-        self._ev_queue.append(EventBatch(buf, handles, plan.first_window, ids, columns))
+        self._ev_queue.append(EventBatch(buf, handles, first_window, ids, columns))
 
     @staticmethod
     def _records(buf, M):
@@ -1224,16 +1212,11 @@ class StreamPool:
         generation -- in the order of the session's columns.  Synchronises."""
         self._need_rule("active")
         s = self._session(h)
-        if self._ev_cells is None or s.slot in self._ev_unmarked:
-            return []
-        streak, length, peak, marks = self._ev_cells
-        book = self.gallery._book
-        ids = [c for c in (book.order if s.classes is None else s.classes) if c in book.slot_of and book.slot_of[c] < marks.shape[1]]
+        ids, at, valid = self._live_cells(s, self._ev_cells)
         if not ids:
             return []
-        at = torch.tensor([book.slot_of[c] for c in ids], device=self.dev)
-        gens = self.gallery.slot_generations().index_select(0, at)
-        on = ((marks[s.slot].index_select(0, at) == gens) & (streak[s.slot].index_select(0, at) < 0) & self._listed(s, at)).tolist()
+        streak, length, peak, _ = self._ev_cells.planes
+        on = (valid & (streak[s.slot].index_select(0, at) < 0)).tolist()
         lens, peaks = length[s.slot].index_select(0, at).tolist(), peak[s.slot].index_select(0, at).tolist()
         return [(c, n, p) for c, live, n, p in zip(ids, on, lens, peaks) if live]
 
@@ -1304,11 +1287,8 @@ class StreamPool:
     def explain_event(self, e, classes=None, k=None):
         """explain() of an event's evidence: the OTAM soft alignment of its window against `classes` (default: the event's own class) or
         against its top-k classes -> clip_fsar_amd.align.Alignment of one clip, through Aligner.align_features.  Changes nothing."""
-        from .align import Aligner
         slot = self._held_event(e, "explain_event")
-        al = getattr(self, "_aligner", None)
-        if al is None or al.gallery is not self.gallery:
-            al = self._aligner = Aligner(self.gallery)
+        al = self._the_aligner()
         if classes is None and k is None:
             classes = [e.class_id]
         return al.align_features(self._ed_store[slot].clone().unsqueeze(0), classes, k)
@@ -1358,58 +1338,28 @@ class StreamPool:
             smoothed = smoothed.index_select(0, index) if by_column else None
             tempo = tempo.index_select(0, index) if tempo is not None else None
         cp = self._class_push(recs, plan.n_windows) if self._keyed and NW else None
-        if self._by_class:                       # one launch, on the session-major logits: a session's rounds stay in sequence
-            smoothed = self._smooth_classes(cp, logits)
-        judged = smoothed if self._by_class else logits
-        if self._baseline is not None:           # likewise one launch per push, after smoothing and before the detector
-            judged = deviation = self._normalize(cp, judged)
-        if cp is not None and self._events is not None:
-            seen = judged if self._contest_rule is None else self._contest(cp, judged)     # the detector alone sees the demoted plane
-            self._detect(handles, recs, plan, seen, cp, after=[s.t + n for s, n in zip(recs, counts)], tempo=tempo)
+        by_class, deviation = self._judge(logits, cp, handles, recs, counts, plan.first_window, tempo=tempo)
+        self._advance(recs, counts, NW)
         offsets = [0]
-        for s, n, nW in zip(recs, counts, plan.n_windows):
-            s.t += n
+        for s, nW in zip(recs, plan.n_windows):
             if by_column and nW:
                 s.state_gen = self._state_gen
                 s.state_layout = getattr(g, "layout_version", None)
             offsets.append(offsets[-1] + nW)
-        self._totals["frames"] += sum(counts)
-        self._totals["windows"] += NW
-        fields = (handles, plan.first_window, offsets, logits, smoothed)
-        if tempo is not None:
-            more = dict(tempo=tempo, rates=self.rates)
-            return (TempoPackedOutput(*fields, **more) if self._baseline is None
-                    else DeviationTempoPackedOutput(*fields, deviation=deviation, **more))
-        return PackedOutput(*fields) if self._baseline is None else DeviationPackedOutput(*fields, deviation=deviation)
+        return _output(PackedOutput, handles, plan.first_window, offsets, logits, smoothed if by_column else by_class, deviation=deviation,
+                       tempo=tempo, rates=self.rates)
 
     # ------------------------------------------------------------------ the pool with a shortlist
-    def _shortlist_planes(self, cap):
-        """seen and merit, each [max_streams, cap] int32, grown with the store as _class_state grows its own: the columns copied, the new
-        columns 0 (never scored); the rows of sessions opened or reset since the last push are zeroed here, on the push's stream"""
-        if self.max_streams * cap > pship.MAX_CELLS:
-            raise ValueError(self._too_many_cells(self.max_streams, cap, "shortlist="))
-        old = None if self._sl_planes is None else self._sl_planes[0].shape[1]
-        if old != cap:
-            new = tuple(torch.zeros(self.max_streams, cap, device=self.dev, dtype=torch.int32) for _ in range(2))
-            if old is not None:
-                for t, was in zip(new, self._sl_planes):
-                    t[:, :old].copy_(was)
-            self._sl_planes = new
-        for slot in sorted(self._sl_unmarked):
-            for t in self._sl_planes:
-                t[slot].zero_()
-        self._sl_unmarked.clear()
-        return self._sl_planes
-
     def _listed(self, s, at):
         """of a pool with a shortlist: which of the session's cells at the store slots `at` (a device index) were scored at its last
         scoring push -- active() and baseline() list those alone; without a shortlist: all of them"""
         if self._shortlist is None:
             return torch.ones(at.shape[0], device=self.dev, dtype=torch.bool)
-        if self._sl_planes is None or s.slot in self._sl_unmarked or not s.tick:
+        if self._sl_cells.planes is None or s.slot in self._sl_cells.forgotten or not s.tick:
             return torch.zeros(at.shape[0], device=self.dev, dtype=torch.bool)
-        inside = at < self._sl_planes[0].shape[1]
-        return inside & (self._sl_planes[0][s.slot].index_select(0, at.clamp(max=self._sl_planes[0].shape[1] - 1)) == s.tick)
+        seen = self._sl_cells.planes[0]
+        inside = at < seen.shape[1]
+        return inside & (seen[s.slot].index_select(0, at.clamp(max=seen.shape[1] - 1)) == s.tick)
 
     def _read_pins(self):
         """the device's pin counts of the pushes since the last reading -> the totals.  Synchronises."""
@@ -1462,10 +1412,10 @@ class StreamPool:
             if order is not None:                  # several rounds: round-major -> session-major, a group must be consecutive
                 W = W.index_select(0, order)
             cap = gens.shape[0]
-            seen, merit = self._shortlist_planes(cap)
-            smooth_marks = self._class_state(cap)[1] if self._by_class else None
-            base_marks = self._baseline_cells(cap)[3] if self._baseline is not None else None
-            ev_streak, ev_marks = (self._event_cells(cap)[0], self._event_cells(cap)[3]) if self._events is not None else (None, None)
+            seen, merit = self._sl_cells.at(cap)
+            smooth_marks = self._smooth_cells.at(cap)[1] if self._by_class else None
+            base_marks = self._bl_cells.at(cap)[3] if self._baseline is not None else None
+            ev_streak, _, _, ev_marks = self._ev_cells.at(cap) if self._events is not None else [None] * 4
             G = len(live)
             if self._sl_tables is None:
                 self._sl_tables = pship.table_uploader(self.dev, self.max_streams)
@@ -1487,16 +1437,9 @@ class StreamPool:
             if self._smooth_tables is None:
                 self._smooth_tables = cship.table_uploader(self.dev, self.max_streams)
             cp = (cplan, gens, sel_slots.view(-1), self._smooth_tables.upload(key_rows))
-            if self._by_class:
-                smoothed = self._smooth_classes(cp, logits)
-            judged = smoothed if self._by_class else logits
-            if self._baseline is not None:
-                judged = deviation = self._normalize(cp, judged)
-            if self._events is not None:
-                # (the padded places of a list carry no store slot: they are no candidates of the contest)
-                shown = judged if self._contest_rule is None else self._contest(cp, judged)
-                self._detect([handles[i] for i in live], [recs[i] for i in live], Plan(None, [plan.first_window[i] for i in live], None, None),
-                             shown, cp, columns=sel_cols, after=[recs[i].t + counts[i] for i in live])
+            # (the padded places of a list carry no store slot: they are no candidates of the contest)
+            rows = lambda per_session: [per_session[i] for i in live]         # the table's rows: the sessions with windows
+            smoothed, deviation = self._judge(logits, cp, rows(handles), rows(recs), rows(counts), rows(plan.first_window), columns=sel_cols)
             if G == S_push:
                 columns, pinned = sel_cols, sel_pin
             else:
@@ -1505,14 +1448,9 @@ class StreamPool:
                     pinned[i].copy_(sel_pin[j])
             counted = torch.stack([n_pins.sum(), (n_pins - K).clamp_(min=0).sum()])
             self._sl_pins = counted if self._sl_pins is None else self._sl_pins + counted
-        for s, n in zip(recs, counts):             # the counters move once every stage is enqueued, as in _run
-            s.t += n
-        self._totals["frames"] += sum(counts)
-        self._totals["windows"] += NW
-        fields = (handles, plan.first_window, offsets, logits, smoothed)
-        more = dict(columns=columns, pinned=pinned, ids=every)
-        return (ShortlistPackedOutput(*fields, **more) if self._baseline is None
-                else DeviationShortlistPackedOutput(*fields, deviation=deviation, **more))
+        self._advance(recs, counts, NW)
+        return _output(PackedOutput, handles, plan.first_window, offsets, logits, smoothed, deviation=deviation, columns=columns,
+                       pinned=pinned, ids=every)
 
     def _topk_shortlist(self, out, k, smoothed):
         """topk of a shortlist pool's output: the top-k places of every window's row (a place without a class is never taken), mapped
@@ -1525,16 +1463,10 @@ class StreamPool:
             raise ValueError("StreamPool.topk: k must be in [1, min(16, K = %d = min(keep, number of classes))], got %r" % (K, k))
         if not nW:
             return (torch.empty(0, k, device=self.dev, dtype=torch.float32), torch.empty(0, k, device=self.dev, dtype=torch.int32))
-        if out.columns.dim() == 1:                 # a session's output
-            n_windows, lists = [nW], out.columns[None]
-        else:
-            n_windows, lists = [w1 - w0 for w0, w1 in zip(out.offsets, out.offsets[1:])], out.columns
-        group = torch.tensor([i for i, n in enumerate(n_windows) for _ in range(n)], device=self.dev, dtype=torch.int64)
+        n_windows, lists = self._shortlist_groups(out)
         rows, _ = grhip.table_rows(n_windows, [K] * len(n_windows), self.T)
         values, index = self.gallery.topk_of_groups(src.contiguous().view(-1), rows, k)
-        found = index != pship.NONE
-        place = torch.where(found, index, torch.zeros_like(index)).long()
-        return values, torch.where(found, lists[group].gather(1, place), index)
+        return values, self._listed_classes(index, pship.NONE, n_windows, lists)
 
     # ------------------------------------------------------------------ enrolment
     def _enrolling_gallery(self):
@@ -1645,6 +1577,14 @@ class StreamPool:
         return shots[cid]
 
     # ------------------------------------------------------------------ explanation
+    def _the_aligner(self):
+        """the pool's Aligner over its gallery, made by the first explanation"""
+        from .align import Aligner
+        al = getattr(self, "_aligner", None)
+        if al is None or al.gallery is not self.gallery:
+            al = self._aligner = Aligner(self.gallery)
+        return al
+
     def explain(self, h, classes=None, k=None, window=None, tempo=None):
         """The OTAM soft alignment of one window of the session (window: a number of enrolable(h); None: the newest complete one) against
         `classes` (registered ids) or against its own top-k classes -> clip_fsar_amd.align.Alignment of one clip: per class the T x T plan,
@@ -1653,12 +1593,9 @@ class StreamPool:
         as they are.  Of an event e: explain(e.session, [e.class_id], window=e.window), as long as the window is in the ring (explain_event(e) of a pool
         with evidence= has no such limit).  tempo (a
         pool with rates=): the index into rates at which the window is read; None: the last one."""
-        from .align import Aligner
         s = self._session(h)
         rate, shift = self._tempo(tempo, "explain")
-        al = getattr(self, "_aligner", None)
-        if al is None or al.gallery is not self.gallery:
-            al = self._aligner = Aligner(self.gallery)
+        al = self._the_aligner()
         ap = al._plan(1, classes, k)                                          # every error before the device is touched
         plan = plan_enroll([(s.slot, s.t)], [(0, window)], self.T, self.stride, self.rate, self.cap, names=["StreamPool: session %d" % h])
         rows = torch.tensor([(plan.positions[0] + shift + j * rate) % self.cap for j in range(self.T)], device=self.dev)

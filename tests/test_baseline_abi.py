@@ -372,9 +372,9 @@ def test_the_baseline_option_on_stub_heads():
     live = _live("live", 4)
     p = StreamPool(live, max_streams=3, smooth=0.5, smooth_by="class", events=rule, baseline=base)       # TypeError without the feature
     h = p.open()
-    assert p.baseline(h) == [] and p._bl_unmarked == {0} == p._ev_unmarked == p._unmarked
+    assert p.baseline(h) == [] and p._bl_cells.forgotten == {0} == p._ev_cells.forgotten == p._smooth_cells.forgotten
     p.reset(h)
-    assert p._bl_unmarked == {0}
+    assert p._bl_cells.forgotten == {0}
     q = StreamPool(_live("live_text", 4), baseline=base)              # no smoothing, no rule: the logits' deviations alone
     assert q._by_class is False and q._events is None and q._keyed and q.baseline(q.open()) == []
     assert StreamPool(live, smooth=0.0, smooth_by="column", baseline=base)._keyed

@@ -364,7 +364,7 @@ def test_smooth_by_on_stub_heads():
     from clip_fsar_amd.text_gallery import TextGallery
     live = _live("live", 4)
     p = StreamPool(live, max_streams=3, smooth=0.5, smooth_by="class")            # TypeError without the feature
-    assert p.smooth_by == "class" and p.alpha == 0.5 and p._state is None and p._marks is None
+    assert p.smooth_by == "class" and p.alpha == 0.5 and p._state is None and p._smooth_cells.planes is None
     assert StreamPool(_live("live_text", 4), smooth=0.25, smooth_by="class").smooth_by == "class"
     assert StreamPool(live, smooth=0.5).smooth_by == "column" == StreamPool(live, smooth=0.5, smooth_by="column").smooth_by
     for g in (SupportGallery(_stub_head(), "cpu"), TextGallery(_stub_head(COMBINE=True), "cpu")):
@@ -377,7 +377,7 @@ def test_smooth_by_on_stub_heads():
     with pytest.raises(ValueError, match="2\\^31"):
         StreamPool(_live("live", 1 << 15), max_streams=1 << 16, smooth=0.5, smooth_by="class")
     inert = StreamPool(live, smooth=0.0, smooth_by="class")                       # smooth = 0: nothing of the class mode is there
-    assert inert._by_class is False and inert._state is None and inert._marks is None
+    assert inert._by_class is False and inert._state is None and inert._smooth_cells is None
     # six-argument construction of the grouped output keeps working; the new field trails and defaults to None
     out = GroupedPackedOutput([0], [0], [0, 0], torch.zeros(0), [0, 0], [2])
     assert out.smoothed is None and GroupedPackedOutput._fields[-1] == "smoothed" and len(GroupedPackedOutput._fields) == 7

@@ -340,7 +340,7 @@ def test_the_events_option_on_stub_heads():
     assert p.stats() == {"frames": 0, "tower_frames": 0, "windows": 0, "events": 0, "events_dropped": 0, "open": 0}
     assert p.take_events() == []
     h = p.open()
-    assert p.active(h) == [] and p._ev_unmarked == {0} == p._unmarked
+    assert p.active(h) == [] and p._ev_cells.forgotten == {0} == p._smooth_cells.forgotten
     assert StreamPool(_live("live_text", 4), events=rule).stats()["events"] == 0                 # no smoothing: the logits are scored
     assert StreamPool(live, smooth=0.0, smooth_by="column", events=rule)._by_class is False
     plain = StreamPool(live, smooth=0.5, smooth_by="class")

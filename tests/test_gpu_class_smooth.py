@@ -268,7 +268,7 @@ def test_class_mode_equals_column_mode_where_both_apply():
             if a.offsets[-1]:
                 assert all(torch.equal(u, v) for u, v in zip(col.topk(a, 3, smoothed=True), cls.topk(b, 3, smoothed=True)))
             windows += a.offsets[-1]
-        assert windows > 40 and cls._state.shape == (4, live.capacity) and cls._marks.dtype == torch.int32
+        assert windows > 40 and cls._smooth_cells.planes[0].shape == (4, live.capacity) and cls._smooth_cells.planes[1].dtype == torch.int32
 
 
 def test_sessions_with_class_lists():
@@ -358,12 +358,12 @@ def test_membership_changes_while_sessions_run(kind):
             pairs.registered(cid)
 
         push((9, 10, 8))
-        assert live.capacity == 6 and pool._state.shape == (4, 6)
+        assert live.capacity == 6 and pool._smooth_cells.planes[0].shape == (4, 6)
         assert pool.enroll(a, 15) == 1                                   # a new class while streams run: the store grows 6 -> 9
         pairs.registered(15)
         assert live.capacity == 9
         push((2, 8, 3))
-        assert pool._state.shape == (4, 9) and pool._marks.shape == (4, 9)
+        assert [t.shape for t in pool._smooth_cells.planes] == [(4, 9), (4, 9)]
         assert pool.enroll(b, 16, join=True) == 1 and pool._sessions[b].classes == [9, 2, 16]
         pairs.registered(16)
         push((3, 2, 0))

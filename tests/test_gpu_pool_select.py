@@ -276,15 +276,15 @@ def _cell_pins(p, h, hold):
     s = p._sessions[h]
     keys = live._columns(None).long()
     t = s.tick + 1
-    if p._sl_planes is None or s.slot in p._sl_unmarked:
+    if p._sl_cells.planes is None or s.slot in p._sl_cells.forgotten:
         return {}
-    width = p._sl_planes[0].shape[1]                     # a store that grew since the last push: its new slots were never scored
+    width = p._sl_cells.planes[0].shape[1]                     # a store that grew since the last push: its new slots were never scored
     inside, at = keys < width, keys.clamp(max=width - 1)
-    seen, merit = (x[s.slot][at] for x in p._sl_planes)
+    seen, merit = (x[s.slot][at] for x in p._sl_cells.planes)
     prev = inside & (seen == t - 1)
     bits = torch.zeros_like(seen)
-    if p._events is not None and p._ev_cells is not None and s.slot not in p._ev_unmarked:
-        streak, _, _, marks = p._ev_cells
+    if p._events is not None and p._ev_cells.planes is not None and s.slot not in p._ev_cells.forgotten:
+        streak, _, _, marks = p._ev_cells.planes
         bits += (prev & (marks[s.slot][at] == live.slot_generations()[keys]) & (streak[s.slot][at] != 0)).int() * EV
     if hold:
         bits += (prev & (merit >= 1) & (t - merit <= hold)).int() * HOLD
@@ -349,7 +349,7 @@ def test_a_gap_ends_nothing_early_and_a_return_starts_anew(world):
             listed_e.append(_place(oe, A, ids))
             listed_b.append(_place(ob, A, ids))
             counts_b.append({c: n for c, _, _, n in pb.baseline(hb)}.get(A))
-            streaks.append(int(pe._ev_cells[0][pe._sessions[he].slot, live.slot_of(A)]))
+            streaks.append(int(pe._ev_cells.planes[0][pe._sessions[he].slot, live.slot_of(A)]))
         events = [e for e in pe.take_events() if e.class_id == A]
         assert [(e.kind, e.window) for e in events[:1]] == [("onset", 1)] and [e.kind for e in events[1:2]] == ["offset"], events
         off_at = events[1].window                                                  # the window that confirmed the offset
@@ -492,7 +492,7 @@ def test_open_with_classes_raises_and_the_store_may_grow_and_reuse_a_slot(world)
         live.add_classes_features(f(4), [7, 8, 9, 10])            # growth past capacity: the planes grow with the store
         assert live.capacity > 8
         o = push(1)
-        assert p._sl_planes[0].shape[1] == live.capacity and HOLD in o.pinned.tolist()       # the held pairs survived the growth
+        assert p._sl_cells.planes[0].shape[1] == live.capacity and HOLD in o.pinned.tolist()       # the held pairs survived the growth
         live.remove_classes([3])
         live.add_classes_features(f(1), [11])                     # "remove 3, add 11" into the freed slot between pushes
         assert live.slot_of(11) is not None

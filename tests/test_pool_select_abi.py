@@ -326,7 +326,7 @@ def test_stream_pool_shortlist_refusals_are_raised_before_the_device_is_touched(
     sl = Shortlist(g, keep=2)
     rule, base = EventRule(0.6, 0.4, 2, 2), Baseline()
     p = StreamPool(g, max_streams=3, smooth=0.5, smooth_by="class", events=rule, baseline=base, shortlist=sl, shortlist_hold=2)
-    assert p._shortlist is sl and p._hold == 2 and p._sl_planes is None
+    assert p._shortlist is sl and p._hold == 2 and p._sl_cells.planes is None
     assert StreamPool(g, shortlist=sl)._hold == 0 and StreamPool(g, shortlist=sl, shortlist_hold=1 << 20)._hold == 1 << 20
     # the two names are keyword-only, and events / baseline are still the 9th and 10th positional arguments
     q = StreamPool(g, 3, 1, 1, 64, 0.5, None, "class", rule, base, shortlist=sl)
@@ -356,17 +356,17 @@ def test_stream_pool_shortlist_refusals_are_raised_before_the_device_is_touched(
     with pytest.raises(ValueError, match=r"open\(classes=\) on a pool with shortlist= is not supported.*out of scope"):
         p.open(classes=[0, 1])
     h = p.open()
-    assert p._sl_unmarked == {0} == p._ev_unmarked and p._sessions[h].tick == 0
+    assert p._sl_cells.forgotten == {0} == p._ev_cells.forgotten and p._sessions[h].tick == 0
     with pytest.raises(ValueError, match=r"enroll\(join=True\) on a pool with shortlist= is not supported.*out of scope"):
         p.enroll(h, 7, join=True)
     assert p.active(h) == [] and p.baseline(h) == []
     assert p.stats() == {"frames": 0, "tower_frames": 0, "windows": 0, "events": 0, "events_dropped": 0, "pins": 0, "pins_dropped": 0,
                          "open": 1}
     p.reset(h)
-    assert p._sl_unmarked == {0}
+    assert p._sl_cells.forgotten == {0}
     # a pool without the option is the pool as it was
     plain = StreamPool(g, smooth=0.5, smooth_by="class", events=rule)
-    assert plain._shortlist is None and not hasattr(plain, "_sl_planes") and "pins" not in plain.stats()
+    assert plain._shortlist is None and not hasattr(plain, "_sl_cells") and "pins" not in plain.stats()
     assert plain.open(classes=[0, 1]) == 0
     # the output types: subclasses of the plain ones with the same tuple
     for plain_type, mine, both in ((pm.PackedOutput, pm.ShortlistPackedOutput, pm.DeviationShortlistPackedOutput),

@@ -88,8 +88,9 @@ def point(head, C, reps, rounds=3):
     n_w = [NW_S] * SESSIONS
     K = min(KEEP, C)
     recs = [p._sessions[h] for h in handles["shortlist"]]
-    planes = [t.clone() for t in (p._event_cells(gens.shape[0])[0], p._event_cells(gens.shape[0])[3], *p._sl_planes,
-                                  p._class_state(gens.shape[0])[1], p._baseline_cells(gens.shape[0])[3])]
+    cap = gens.shape[0]
+    planes = [t.clone() for t in (p._ev_cells.at(cap)[0], p._ev_cells.at(cap)[3], *p._sl_cells.planes,
+                                  p._smooth_cells.at(cap)[1], p._bl_cells.at(cap)[3])]
     uploader = pship.table_uploader("cuda", SESSIONS)
     now = {"tick": recs[0].tick}
     st = {}
@@ -117,7 +118,7 @@ def point(head, C, reps, rounds=3):
               "grouped_otam": lambda: st.update(out=sl._exact(st["q"][0], st["q"][1], st["sel"][1], n_w, K)),
               "smooth_classes": lambda: st.update(y=p._smooth_classes(keyed(), st["out"][0])),
               "baselines": lambda: st.update(z=p._normalize(keyed(), st["y"])),
-              "detector": lambda: p._detect(handles["shortlist"], recs, res["shortlist"], st["z"], keyed(), columns=st["sel"][0])}
+              "detector": lambda: p._detect(handles["shortlist"], recs, res["shortlist"].first_window, st["z"], keyed(), columns=st["sel"][0])}
     stage_ms = {}
     for k, fn in stages.items():
         stage_ms[k] = round(_time_ms(fn, reps), 4)
