@@ -218,10 +218,12 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
 # (clip_fsar_amd.align), the tempo windows of a stream pool with rates=, and event evidence (clip_fsar_amd.evidence): an event's
 # window copied out of the ring into a device store by the push that detected it, and the still-frame gate of a stream pool with
 # still= (clip_fsar_amd.still): frames that did not change skip the tower, and the contest of a stream pool with contest=
-# (clip_fsar_amd.contest): only a window's leading classes reach the detector.  ExtLib values again; the open registry.
+# (clip_fsar_amd.contest): only a window's leading classes reach the detector, and the history search of a stream pool with history=
+# (clip_fsar_amd.history): a class's best non-overlapping occurrences in the windows a store that outlives the ring still holds.
+# ExtLib values again; the open registry.
 PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
                             os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
-               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still", "contest")}
+               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still", "contest", "history")}
 
 
 def plugin_lib_names() -> list:

@@ -39,6 +39,9 @@
     w.push({a: frames}); w.last_kept()                                # {a: (True, False, ..)}: which frames went through the tower
     k = StreamPool(live_gallery, events=EventRule(on=0.6, off=0.4), contest=Contest(top=1))              # clip_fsar_amd.contest
     k.take_events(); k.leaders(out)                                   # events of a window's best class alone; (columns [nW, top], counts [nW])
+    y = StreamPool(live_gallery, stride=2, history=History(frames=4096))                                  # clip_fsar_amd.history
+    y.searchable(a); r = y.search([7, "kite"], top=16); r.hits[7]     # [Hit(session, class_id, window, score, tempo)], best first
+    y.hit_features(hit); y.explain_hit(hit); y.enroll_hit(hit, "kite")                # on a hit whose window the history still holds
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -129,6 +132,16 @@ event counts a window below `off` and ends after min_off windows out of the lead
 detector sees that plane: the push returns the bits it returns without the option (a shortlist pool's pins follow the detector's cells, so an
 outranked pair's pin lapses with its event).  leaders(out) recomputes a push's leading columns on the device.  The stage keeps no state.
 
+history=History(frames=F) (clip_fsar_amd.history, which states the store, the plane and the peak rule; a LiveGallery): a store
+[max_streams, F, E] that outlives the ring, F >= cap, made by the first push; every round of every push writes its rows there right beside
+the ring write, with the ring's own kernel (cfsp_ring_put, the store as its ring: frame f at [slot, f mod F]).  The push returns the bits it
+returns without the option.  searchable(h) is enrolable_windows over F; search(classes, ...) gathers the held windows of the open sessions
+asked for (cfsp_window_sequences over one table, the store as its ring), scores them with classify_features(classes=) chunk by chunk into
+a plane [NW, K] and runs libclipfsar_history.so (clip_fsar_amd.history_hip, two launches over the gather's table) on it: per class the
+local maxima within `separation` windows of one session -- a local-maximum filter, not greedy suppression; a plateau yields its first
+window -- and of those the `top` highest across sessions.  It synchronises once, to read the hit records.  hit_features, explain_hit and
+enroll_hit read a hit's window out of the store the way enroll and explain read the ring.  The option adds nothing to stats().
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -150,6 +163,7 @@ from . import evidence_hip as edhip
 from . import events_hip as evhip
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
+from . import history_hip as hship
 from . import pool_hip as php
 from . import pool_select_hip as pship
 from . import still_hip as skhip
@@ -159,6 +173,8 @@ from .contest import Contest
 from .events import EventRule, translate
 from .evidence import MISSED, Evidence, EvidenceEvent, keep0
 from .gallery import _GalleryBase
+from .history import (History, Hit, SearchResult, check_min_score, check_separation, check_top, device_separation, largest_frames,
+                      plan_search)
 from .ingest import FrameIngest
 from .still import StillGate, plan_still
 from .stream import StreamOutput, window_plan
@@ -398,9 +414,9 @@ class _Cells:
 
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
-                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, contest=None, events=None,
-                 baseline=None):
-        # shortlist=, shortlist_hold=, rates=, evidence=, still= and contest= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+                 *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, contest=None, history=None,
+                 events=None, baseline=None):
+        # shortlist=, shortlist_hold=, rates=, evidence=, still=, contest= and history= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
             raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
@@ -458,6 +474,8 @@ class StreamPool:
             if events is None:
                 raise ValueError("StreamPool: contest= is given without events= -- the contest decides which classes of a window reach "
                                  "the detector; build the pool with events=EventRule(...) as well")
+        if history is not None:
+            self._check_history(gallery, history, (gallery.T - 1) * rate + max_push, max_streams)
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
@@ -544,6 +562,12 @@ class StreamPool:
             self._sk_lists = skhip.ListUploader(self.dev)
             self._sk_work = None                 # still_hip.changed's workspace, grown on demand
             self._sk_last = {}                   # last_kept()'s answer
+        self._history = history                  # the History, or None: nothing below is there
+        if history is not None:
+            self._hs_store = None                # [max_streams, F, E] fp32: frame f of a session at [slot, f mod F]; made by the first push
+            self._hs_tables = php.TableUploader(self.dev, 2 * max_streams)   # a round's two tables in one upload; a search's one
+            self._hs_X = None                    # a search's gathered windows [rows, T, E], grown on demand
+            self._hs_work = None                 # history_hip.peaks' workspace, grown on demand
         if ingest is not None and not isinstance(ingest, FrameIngest):
             raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
         if ingest is not None:
@@ -574,6 +598,28 @@ class StreamPool:
             raise ValueError("StreamPool: rates= together with shortlist= is not supported -- tempo windows of a shortlisted pool are out "
                              "of scope; build the pool with one of the two")
         return tuple(rates)
+
+    @staticmethod
+    def _check_history(gallery, history, cap, max_streams):
+        """every refusal of history= of the constructor, before anything is allocated"""
+        from .live_gallery import LiveGallery
+        from .live_text_gallery import LiveTextGallery
+        from .text_gallery import TextGallery
+        if not isinstance(history, History):
+            raise TypeError("StreamPool: history must be a History, got %s" % type(history).__name__)
+        if isinstance(gallery, (TextGallery, LiveTextGallery)):
+            raise ValueError("StreamPool: history= on a %s is not supported -- a softmax over the searched classes alone is another "
+                             "quantity than the one over every class; use a LiveGallery" % type(gallery).__name__)
+        if not isinstance(gallery, LiveGallery):
+            raise ValueError("StreamPool: history= needs a gallery that scores class subsets and registers from features (a "
+                             "LiveGallery), not a %s" % type(gallery).__name__)
+        if history.frames < cap:
+            raise ValueError("StreamPool: history.frames = %d is below the ring's cap = (T - 1) * rate + max_push = %d -- a history "
+                             "shorter than the ring is the ring; give at least %d frames" % (history.frames, cap, cap))
+        most = largest_frames(max_streams, gallery.E)
+        if history.frames > most:
+            raise ValueError("StreamPool: history.frames = %d x max_streams = %d rows of E = %d floats break the pool library's 32-bit "
+                             "item limit -- the largest frames that fits is %d" % (history.frames, max_streams, gallery.E, most))
 
     # ------------------------------------------------------------------ sessions
     def open(self, classes=None):
@@ -865,12 +911,14 @@ class StreamPool:
             raise ValueError("StreamPool: a push takes a non-empty dict {session: uint8 [n, H, W, 3] frames}")
         return self._split(self.push_u8_packed(list(clips.values()), list(clips)))
 
-    def _gathered(self, eng, plan, feats):
+    def _gathered(self, eng, plan, feats, recs=None):
         """The device side of a push up to scoring: per round one table and one ring write, then per chunk of its windows one gather.
         Yields (round, its table, its windows nW, chunk w0, w1, the chunk's windows X [w1 - w0, T, E]); a round without windows yields
         nothing.  Of a pool with rates=: X is [(w1 - w0) * R, T, E], the R tempos of every window, rows ordered (window, tempo), and a
-        chunk holds as many windows as their R sequences each fit classify_features."""
+        chunk holds as many windows as their R sequences each fit classify_features.  recs: the push's session records -- a pool
+        with history= writes every round's rows into its store as well."""
         T = self.T
+        done = [0] * len(plan.first_window)      # frames of each session the rounds so far have written
         R = 1 if self.rates is None else len(self.rates)
         per = max(1, eng.max_frames // (T * R))  # classify_features scores that many clips per chunk: gather no more at a time
         for rnd in plan.rounds:
@@ -878,8 +926,13 @@ class StreamPool:
                 piece = feats
             else:                                # a later round's frames lie apart in the packed features: pack them for the ring write
                 piece = torch.cat([feats[f0:f0 + n] for f0, n in rnd.src], 0)
-            table = self._tables.upload(rnd.rows)
-            php.ring_put(piece, self._ring, table)
+            if self._history is None:
+                table = self._tables.upload(rnd.rows)
+                php.ring_put(piece, self._ring, table)
+            else:                                # the store's table rides behind the ring's: one upload, two ring writes
+                table, held = self._history_tables(rnd, recs, done)
+                php.ring_put(piece, self._ring, table)
+                php.ring_put(piece, self._hs_store, held)
             nW = sum(r[php.NW] for r in rnd.rows)
             if nW == 0:
                 continue
@@ -907,7 +960,7 @@ class StreamPool:
             logit_offsets.append(logit_offsets[-1] + nW * C)
         logits = torch.empty(logit_offsets[-1], device=self.dev, dtype=torch.float32)
         done = [0] * len(recs)                   # windows of each session scored so far: its block fills in window order
-        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats, recs):
             # the chunk's windows session by session: row j of the round holds windows WIN_OFF .. WIN_OFF + NW - 1 of the round's list
             part = [(i, max(0, min(w1, r[php.WIN_OFF] + r[php.NW]) - max(w0, r[php.WIN_OFF]))) for i, r in zip(rnd.members, rnd.rows)]
             part = [(i, n) for i, n in part if n]
@@ -1322,7 +1375,7 @@ class StreamPool:
             self._state = torch.empty(self.max_streams, C, device=self.dev, dtype=torch.float32)
             self._state_gen += 1
         g0 = 0
-        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats, recs):
             out = logits[g0:g0 + nW]
             if tempo is None:
                 out[w0:w1].copy_(g.classify_features(X))
@@ -1395,7 +1448,7 @@ class StreamPool:
         # ---- the device: ring writes and gathers, round by round
         W = torch.empty(NW, T, self.E, device=self.dev, dtype=torch.float32)
         g0 = 0
-        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats):
+        for rnd, table, nW, w0, w1, X in self._gathered(eng, plan, feats, recs):
             W[g0 + w0:g0 + w1].copy_(X)
             if w1 == nW:
                 g0 += nW
@@ -1497,14 +1550,15 @@ class StreamPool:
                              % (what, self.rates, R - 1, tempo))
         return self.rates[tempo], (self.T - 1) * (self.rate - self.rates[tempo])
 
-    def _ring_sequences(self, trows, slots, positions, classes, rate=None):
+    def _ring_sequences(self, trows, slots, positions, classes, rate=None, ring=None):
         """one launch: the support sequences X0 [n, T+1, E] of the ring windows (slot, position), each closed by trows[classes[i]];
-        rate: the frames' distance in the ring (None: the pool's)"""
+        rate: the frames' distance in the ring (None: the pool's); ring: what is read, [max_streams, its cap, E], the positions
+        counting modulo that cap (None: the pool's ring; the history store of a pool with history=)"""
         n = len(slots)
         if self._enroll_tables is None or self._enroll_tables.max_rows < n:
             self._enroll_tables = enhip.table_uploader(self.dev, max(1024, n))
         X0 = torch.empty(n, self.T + 1, self.E, device=self.dev, dtype=torch.float32)
-        enhip.ring_sequences(self._ring, trows, self._enroll_tables.upload(enhip.table_rows(slots, positions, classes)), X0,
+        enhip.ring_sequences(self._ring if ring is None else ring, trows, self._enroll_tables.upload(enhip.table_rows(slots, positions, classes)), X0,
                              self.rate if rate is None else rate)
         return X0
 
@@ -1633,3 +1687,145 @@ class StreamPool:
         if nW:
             ghip.topk(src.contiguous(), k, values, index)
         return values, index
+
+    # ------------------------------------------------------------------ history search
+    def _history_tables(self, rnd, recs, done):
+        """the two tables of one round in one upload -> (the ring's, as _tables.upload(rnd.rows) gives it; the history store's: the same
+        rows with PUT_POS counting modulo F and no windows, for the ring's own kernel to write the round's rows right beside the ring
+        write).  done: the frames of each session the push's earlier rounds wrote, advanced here."""
+        F = self._history.frames
+        if self._hs_store is None:
+            self._hs_store = torch.empty(self.max_streams, F, self.E, device=self.dev, dtype=torch.float32)
+        rows = []
+        for i, r in zip(rnd.members, rnd.rows):
+            rows.append([r[php.SLOT], (recs[i].t + done[i]) % F, r[php.N], r[php.FEAT_OFF], 0, 0, 0, 0])
+            done[i] += r[php.N]
+        both, S = self._hs_tables.upload(rnd.rows + rows), len(rows)
+        return php.Table(both.host[:S], both.dev[:S], S), php.Table(both.host[S:], both.dev[S:], S)
+
+    def _need_history(self, what):
+        if self._history is None:
+            raise ValueError("StreamPool.%s: this pool keeps no history (build it with history=History(frames=...))" % what)
+
+    def searchable(self, h):
+        """range of the session's window numbers that search() scans and the *_hit methods accept: complete, and their first frame
+        still in the history store"""
+        self._need_history("searchable")
+        return enrolable_windows(self._session(h).t, self.T, self.stride, self.rate, self._history.frames)
+
+    def search(self, classes, sessions=None, top=16, min_score=None, separation=None, last=None, tempo=None):
+        """Where did `classes` (1 to 64 registered ids, no repeats) happen in the windows the history still holds?  -> SearchResult
+        (clip_fsar_amd.history, which states the plane and the rule): hits {class id: [Hit(session, class_id, window, score, tempo)],
+        best first}, at most `top` per class and no two of one session and class within `separation` windows of each other (default:
+        the largest distance at which two windows share a frame); peaks {class id: the count before top cut it}; windows scanned; the
+        plane scores [NW, K] on the device with its sessions, first_window and offsets.  sessions: None -- every open session in handle
+        order -- or a list, in that order; min_score: only scores >= it (as fp32) count; last=n: only windows completed by one of a
+        session's newest n frames; tempo (a pool with rates=): the index into rates at which every window is read, None: the last.
+        One gather and one classify_features per chunk of windows, two launches for the peaks, one synchronisation.  Changes nothing."""
+        self._need_history("search")
+        what = "StreamPool.search"
+        g = self.gallery
+        from .live_gallery import plan_columns
+        ids = list(classes) if isinstance(classes, (list, tuple)) else None
+        if ids is None:
+            raise TypeError("%s: classes must be a list of registered class ids, got %s" % (what, type(classes).__name__))
+        plan_columns(g._book, ids, what)
+        if len(ids) > hship.MAX_CLASSES:
+            raise ValueError("%s: %d classes -- one search takes 1 to %d; split the list" % (what, len(ids), hship.MAX_CLASSES))
+        if sessions is None:
+            handles = self.sessions
+        else:
+            handles = list(sessions) if isinstance(sessions, (list, tuple)) else None
+            if handles is None:
+                raise TypeError("%s: sessions must be None or a list of open sessions, got %s" % (what, type(sessions).__name__))
+            if len(set(handles)) != len(handles):
+                raise ValueError("%s: a session appears twice in sessions=: %r" % (what, handles))
+        recs = [self._session(h) for h in handles]
+        check_top(top, what)
+        floor = check_min_score(min_score, what)
+        sep = check_separation(((self.T - 1) * self.rate) // self.stride if separation is None else separation, what)
+        if last is not None and (isinstance(last, bool) or not isinstance(last, int) or last < 1):
+            raise ValueError("%s: last must be None or an integer >= 1 (frames), got %r" % (what, last))
+        rate, shift = self._tempo(tempo, "search")
+        at_tempo = None if self.rates is None else (len(self.rates) - 1 if tempo is None else tempo)
+        T, K, F = self.T, len(ids), self._history.frames
+        plan = plan_search([(s.slot, s.t) for s in recs], T, self.stride, self.rate, F, last, shift)
+        NW = plan.offsets[-1]
+        sep = device_separation(sep, plan.n_windows, what)
+        if NW * K > hship.MAX_PLANE:
+            raise ValueError("%s: %d windows x %d classes -- a plane holds at most 2^30 scores; search fewer sessions or classes, or "
+                             "give last=" % (what, NW, K))
+        scores = torch.empty(NW, K, device=self.dev, dtype=torch.float32)
+        result = lambda hits, peaks: SearchResult(dict(zip(ids, hits)), dict(zip(ids, peaks)), NW, scores, handles, plan.first_window,
+                                                  plan.offsets)
+        if not NW:                                 # nothing is held (or no session is open): nothing is launched
+            return result([[] for _ in ids], [0] * K)
+        eng = self._ready()
+        table = self._hs_tables.upload(plan.rows)
+        per = max(1, eng.max_frames // T)          # classify_features scores that many clips per chunk: gather no more at a time
+        if self._hs_X is None or self._hs_X.shape[0] < min(NW, per):
+            self._hs_X = torch.empty(min(NW, per), T, self.E, device=self.dev, dtype=torch.float32)
+        for w0 in range(0, NW, per):
+            w1 = min(NW, w0 + per)
+            X = self._hs_X[:w1 - w0]
+            php.window_sequences(self._hs_store, X, table, NW, w0, w1, T, self.stride, rate)
+            scores[w0:w1].copy_(g.classify_features(X, classes=ids))
+        # the records in one buffer, so that one copy brings them down: n_hits [K], n_peaks [K], hit_rows [K, top], hit_scores [K, top]
+        buf = torch.empty(2 * K + 2 * K * top, device=self.dev, dtype=torch.int32)
+        n_hits, n_peaks = buf[:K], buf[K:2 * K]
+        hit_rows = buf[2 * K:2 * K + K * top].view(K, top)
+        hit_scores = buf[2 * K + K * top:].view(torch.float32).view(K, top)
+        work = self._work("_hs_work", hship.workspace_words(NW, K))
+        hship.peaks(scores, work, hit_rows, hit_scores, n_hits, n_peaks, table, sep, floor, top)
+        host = buf.cpu()                           # the search's one synchronisation
+        counts, peaks = host[:K].tolist(), host[K:2 * K].tolist()
+        rows = host[2 * K:2 * K + K * top].view(K, top).tolist()
+        values = host[2 * K + K * top:].view(torch.float32).view(K, top).tolist()
+        owner = [i for i, n in enumerate(plan.n_windows) for _ in range(n)]          # plane row -> its session's place in the search
+        hits = []
+        for c, n, rr, vv in zip(ids, counts, rows, values):
+            order = sorted(range(n), key=lambda j: (-vv[j], rr[j]))                  # descending score, then plane row
+            hits.append([Hit(handles[owner[rr[j]]], c, plan.first_window[owner[rr[j]]] + rr[j] - plan.offsets[owner[rr[j]]], vv[j], at_tempo)
+                         for j in order])
+        return result(hits, peaks)
+
+    def _held_hit(self, h, what):
+        """every refusal of a *_hit method -> (the session's record, the store position of the first frame of the hit's window read
+        at the hit's tempo, the rate it is read at)"""
+        self._need_history(what)
+        if not isinstance(h, Hit):
+            raise TypeError("StreamPool.%s: takes a Hit that search() returned, got %s" % (what, type(h).__name__))
+        s = self._session(h.session)
+        rate, shift = self._tempo(h.tempo, what)
+        F = self._history.frames
+        plan = plan_enroll([(s.slot, s.t)], [(0, h.window)], self.T, self.stride, self.rate, F, names=["StreamPool: session %d" % h.session])
+        return s, (plan.positions[0] + shift) % F, rate
+
+    def hit_features(self, h):
+        """[T, E] fp32, a copy: the tower rows of a hit's window (read at the hit's tempo) out of the history store, as long as
+        h.window is in searchable(h.session).  One launch, the one enroll reads the ring with."""
+        s, pos, rate = self._held_hit(h, "hit_features")
+        zero = torch.zeros(1, self.E, device=self.dev, dtype=torch.float32)           # the closing row of a support sequence: dropped
+        return self._ring_sequences(zero, [s.slot], [pos], [0], rate, ring=self._hs_store)[0, :self.T].clone()
+
+    def explain_hit(self, h, classes=None, k=None):
+        """explain() of a hit: the OTAM soft alignment of its window against `classes` (default: the hit's own class) or against its
+        top-k classes -> clip_fsar_amd.align.Alignment of one clip, through Aligner.align_features.  Changes nothing."""
+        self._held_hit(h, "explain_hit")
+        al = self._the_aligner()
+        if classes is None and k is None:
+            classes = [h.class_id]
+        return al.align_features(self.hit_features(h).unsqueeze(0), classes, k)
+
+    def enroll_hit(self, h, class_id, text=None):
+        """enroll() of a hit: its window becomes a shot of class_id -- of a registered class a further one, of an unknown id the first
+        of a new class (its text from TEST.CLASS_NAME or from `text`, {class id: name or [E] row}) -> the class's shot count.
+        Through the gallery's add_shots_features / add_classes_features; nothing of any session changes."""
+        self._held_hit(h, "enroll_hit")
+        g = self._enrolling_gallery()
+        cid = g._shot_ids([class_id])[0]
+        feats = self.hit_features(h).unsqueeze(0)
+        if cid in g._book.slot_of:
+            return list(g.add_shots_features(feats, [cid]))[0]
+        g.add_classes_features(feats, [cid], text)
+        return 1
