@@ -22,6 +22,9 @@ in place, and between growths (1.5 x when full) the store's address does not mov
     g.slot_revision(slot)                        # host only: rises whenever the slot's prototype rows are written, further shots included, so what
                                                  # is derived from a prototype (clip_fsar_amd.shortlist.Shortlist's coarse rows) knows when to follow
 
+    g = LiveGallery(head, device, ledger=ShotLedger(shots=4096))       # keyword-only (clip_fsar_amd.ledger): every shot's addend is kept too,
+    g.last_shots; g.shot_list(9); g.remove_shots([s]); g.move_shots([s], 2); g.shot_fit(9)    # so single shots leave, move and are audited
+
 A class is the mean of its shots, so the store also keeps every class's running SUM (of context2's outputs; with MERGE_BEFORE of the
 support sequences before context2) and its shot count: further shots continue the sum in cfsg_segment_mean's operation order
 (cfsl_accumulate).  Serves the default eval branch, like SupportGallery, and is accepted wherever one is (WindowStream, StreamPool); the
@@ -36,6 +39,8 @@ import torch
 
 from . import gallery_hip as ghip
 from . import groups_hip as grhip
+from . import ledger as ldg
+from . import ledger_hip as ldhip
 from . import live_hip as lhip
 from .gallery import LAMBDA, _flag, _GalleryBase
 
@@ -192,14 +197,23 @@ class GroupedLogits:
 
 # ---------------------------------------------------------------------------------------------------------------- the gallery
 class LiveGallery(_GalleryBase):
-    def __init__(self, head, device="cuda", capacity=64):
+    def __init__(self, head, device="cuda", capacity=64, *, ledger=None):
         head = getattr(head, "head", head)                 # BaseVideoModel -> its CNN_OTAM_CLIPFSAR head
         self._check_branch(head.args)
         if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
             raise ValueError("LiveGallery: capacity must be an integer >= 1, got %r" % (capacity,))
+        if ledger is not None and not isinstance(ledger, ldg.ShotLedger):
+            raise TypeError("LiveGallery: ledger must be a ShotLedger (clip_fsar_amd.ledger) or None, got %r" % (ledger,))
         self._setup(head, device)
         if self.T > lhip.MAX_T:
             raise ValueError("LiveGallery: T = %d frames, the live library scores at most %d" % (self.T, lhip.MAX_T))
+        if ledger is not None and self.E % 4:
+            raise ValueError("LiveGallery: ledger= needs E %% 4 == 0 (the ledger library moves 16-byte pieces), got E = %d" % self.E)
+        self._ledger = ledger                              # the option; without it nothing below the next four lines exists
+        self._lbook = None if ledger is None else ldg.new_ledger_book(ledger.shots)
+        self._lstore = self._ltables = None                # the addend store (and the features'), allocated by the first adding call
+        self._lpending = None                              # (the Book a plan returned, the ledger slots the call needs so far)
+        self._levicted, self._last_shots, self._lcapped = {}, [], set()
         self._capacity = capacity
         self._store = None                                 # allocated by the first call that needs the device
         self._retired = []                                 # (outgrown store, the event behind the work queued on it)
@@ -224,6 +238,9 @@ class LiveGallery(_GalleryBase):
         version = 0 if self._book is None else self._book.version + bool(self._book.order)
         cap = self._store_cap() if self._store is not None else self._capacity
         self._install(new_book(cap)._replace(version=version), renew=True)
+        if self._ledger is not None:                       # the ledger is empty; serials are never reused
+            self._lbook = ldg.new_ledger_book(self._ledger.shots, self._lbook.next_serial)
+            self._ledger_forget()
 
     def _install(self, book, renew=False):
         """the Book a call leaves behind.  The slots' generations follow it: a slot that was freed, or whose class is another one now, gets
@@ -328,12 +345,14 @@ class LiveGallery(_GalleryBase):
             self._tables = lhip.table_uploader(self.dev, TABLE_ROWS)
         return self._tables.upload([list(r) for r in rows])
 
-    def _update_sequences(self, eng, X0, offs, rows):
+    def _update_sequences(self, eng, X0, offs, rows, shots=None):
         """Support sequences X0 [Nv, T+1, E], grouped by class (class i = sequences offs[i] .. offs[i+1]-1; rows: the classes' (slot, off,
         n, prior)) into the store: sums, prototypes, norms.  SupportGallery's launch sequence after the support sequences -- context2 class
-        by class -- with cfsl_accumulate in the place of cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone."""
+        by class -- with cfsl_accumulate in the place of cfsg_segment_mean (prior = 0: its bits) and the norms of the touched slots alone.
+        shots (a gallery with ledger=): (the classes' ids, the origin) -- every sequence's addend goes into the ledger beside the sum."""
         st, T, E, n = self._store, self.T, self.E, len(rows)
         self._touch_slots([r[0] for r in rows])
+        plan, put = (None, None) if self._ledger is None else self._ledger_plan_put(shots[0], rows, shots[1])
         Y = None if self.merge_before else self._context2_by_class(eng, X0, offs)       # (:2955-2956)
         for c0 in range(0, n, TABLE_ROWS):
             c1 = min(n, c0 + TABLE_ROWS)
@@ -342,13 +361,24 @@ class LiveGallery(_GalleryBase):
             if self.merge_before:                             # class means BEFORE context2 (:2949-2954), the text row included
                 seqs = torch.empty(c1 - c0, T + 1, E, device=self.dev, dtype=torch.float32)
                 lhip.accumulate(X0[v0:v1], st["sums"], seqs, table, by_slot=False)
-                Y1 = self._context2_by_class(eng, seqs, list(range(c1 - c0 + 1)))
-                P = torch.empty(c1 - c0, T, E, device=self.dev, dtype=torch.float32)
-                ghip.segment_mean(Y1, torch.arange(c1 - c0 + 1, device=self.dev, dtype=torch.int32), P)     # a mean over one sequence
-                st["P"].index_copy_(0, torch.tensor([r[0] for r in rows[c0:c1]], device=self.dev), P)
+                self._prototypes_of_means(eng, seqs, [r[0] for r in rows[c0:c1]])
             else:                                             # prototype = class mean of context2's first T rows (:2957-2962)
                 lhip.accumulate(Y[v0:v1], st["sums"], st["P"], table, by_slot=True)
+            if put is not None:                               # exactly the rows the accumulate above summed, and the raw tower rows
+                ldhip.put(X0[v0:v1] if self.merge_before else Y[v0:v1], self._lstore["addends"], put[v0:v1])
+                if self._ledger.features:
+                    ldhip.put(X0[v0:v1], self._lstore["features"], put[v0:v1])
             lhip.slot_norms(st["P"], st["pn"], table)
+        if self._ledger is not None:                          # the launches are queued: the ledger's book follows, as the gallery's will
+            self._ledger_install_put(plan)
+
+    def _prototypes_of_means(self, eng, seqs, slots):
+        """MERGE_BEFORE: the classes' mean sequences seqs [n, T+1, E] through context2, class by class, into the prototypes of `slots`"""
+        n, T, E = len(slots), self.T, self.E
+        Y1 = self._context2_by_class(eng, seqs, list(range(n + 1)))
+        P = torch.empty(n, T, E, device=self.dev, dtype=torch.float32)
+        ghip.segment_mean(Y1, torch.arange(n + 1, device=self.dev, dtype=torch.int32), P)     # a mean over one sequence
+        self._store["P"].index_copy_(0, torch.tensor(slots, device=self.dev), P)
 
     # ------------------------------------------------------------------ registration, shots, removal
     # Each has a pixel form and a feature form, which differ in how the support sequences come about: `sequences(ids_of_video, classes,
@@ -360,39 +390,47 @@ class LiveGallery(_GalleryBase):
         about the classes"""
         trows = self._text_rows(eng, new_ids, text)
         counts = [sum(1 for v in ids_of_video if v == c) for c in new_ids]
-        return trows, counts, plan_add(self._book if book is None else book, new_ids, counts, self._name)
+        plan = plan_add(self._book if book is None else book, new_ids, counts, self._name)
+        self._ledger_room(book, plan.book, dict(zip(new_ids, counts)))
+        return trows, counts, plan
 
-    def _register_sequences(self, eng, trows, counts, plan, sequences):
-        """the device work of a registration planned by _plan_classes; sequences(trows) -> (X0, offs).  -> the new column indices"""
+    def _register_sequences(self, eng, trows, counts, plan, sequences, origin="enroll"):
+        """the device work of a registration planned by _plan_classes; sequences(trows) -> (X0, offs).  -> the new column indices.
+        origin (a gallery with ledger=): what the shots' records say; the feature entries and StreamPool's enrolment leave the default"""
         st = self._ensure_store(plan.book.cap)
         offs = [0]
         for k in counts:
             offs.append(offs[-1] + k)
         X0, seq_offs = sequences(trows)
         assert seq_offs == offs
-        self._update_sequences(eng, X0, offs, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)])
+        self._update_sequences(eng, X0, offs, [(s, offs[i], counts[i], 0) for i, s in enumerate(plan.slots)],
+                               (plan.book.order[len(plan.book.order) - len(plan.slots):], origin))
         self._write_text_rows(st, plan.slots, trows)
         C0 = len(self._book.order)
         self._install(plan.book)
+        self._ledger_evict(eng)
         return list(range(C0, C0 + len(plan.slots)))
 
     def _write_text_rows(self, st, slots, trows):
         """the new classes' text rows into their slots (LiveTextGallery: and their norms)"""
         st["text"].index_copy_(0, torch.tensor(slots, device=self.dev), trows)
 
-    def _shots_sequences(self, eng, plan, sequences):
+    def _shots_sequences(self, eng, plan, sequences, origin="enroll"):
         """the device work of further shots planned by plan_shots; sequences(trows) -> (X0, offs).  -> the classes' shot counts"""
         st = self._store
         trows = st["text"].index_select(0, torch.tensor([r[0] for r in plan.rows], device=self.dev))
         X0, offs = sequences(trows)
-        self._update_sequences(eng, X0, offs, plan.rows)
+        self._update_sequences(eng, X0, offs, plan.rows, (plan.classes, origin))
         self._book = plan.book                              # the columns did not change: _ids and the device lists stay
-        return [plan.book.shots[c] for c in plan.classes]
+        self._ledger_evict(eng)
+        return [self._book.shots[c] for c in plan.classes]
 
-    def _add_classes(self, eng, src, class_of_video, text, sequences_of):
+    def _add_classes(self, eng, src, class_of_video, text, sequences_of, origin="enroll"):
         ids_of_video, new_ids = self._video_classes(src, class_of_video, text)
         trows, counts, plan = self._plan_classes(eng, ids_of_video, new_ids, text)
-        return self._register_sequences(eng, trows, counts, plan, lambda trows: sequences_of(src, ids_of_video, new_ids, trows))
+        cols = self._register_sequences(eng, trows, counts, plan, lambda trows: sequences_of(src, ids_of_video, new_ids, trows), origin)
+        self._last_in_video_order(ids_of_video, new_ids)
+        return cols
 
     def _shot_ids(self, class_of_video):
         ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (
@@ -401,21 +439,25 @@ class LiveGallery(_GalleryBase):
 
     def _plan_shots(self, ids, book=None):
         """plan_shots on `book`, default the gallery's (StreamPool.enroll_windows plans a whole call on a book of its own)"""
-        return plan_shots(self._book if book is None else book, ids, self._name)
+        plan = plan_shots(self._book if book is None else book, ids, self._name)
+        self._ledger_room(book, plan.book, {c: r[2] for c, r in zip(plan.classes, plan.rows)})
+        return plan
 
-    def _add_shots(self, eng, src, class_of_video, sequences_of):
+    def _add_shots(self, eng, src, class_of_video, sequences_of, origin="enroll"):
         ids = self._shot_ids(class_of_video)
         if len(ids) != src.shape[0]:
             raise ValueError("%s: %d videos but %d class ids" % (self._name, src.shape[0], len(ids)))
         plan = self._plan_shots(ids)
-        return self._shots_sequences(eng, plan, lambda trows: sequences_of(src, ids, plan.classes, trows))
+        counts = self._shots_sequences(eng, plan, lambda trows: sequences_of(src, ids, plan.classes, trows), origin)
+        self._last_in_video_order(ids, plan.classes)
+        return counts
 
     def add_classes(self, videos, class_of_video, text=None):
         """SupportGallery.add_classes: the same arguments, errors, return value (the new classes' column indices) and prototypes; nothing but
         the new classes is written."""
         eng = self._fresh_engine()
         videos = self._check_videos(videos, "videos")
-        return self._add_classes(eng, videos, class_of_video, text, lambda *a: self._support_sequences(eng, *a))
+        return self._add_classes(eng, videos, class_of_video, text, lambda *a: self._support_sequences(eng, *a), "add_classes")
 
     def add_classes_features(self, feats, class_of_video, text=None):
         """add_classes of clips whose tower features feats [Nv, T, E] fp32 (device) exist already (a cache, a stream pool's ring): the same
@@ -430,7 +472,7 @@ class LiveGallery(_GalleryBase):
         order."""
         eng = self._fresh_engine()
         videos = self._check_videos(videos, "videos")
-        return self._add_shots(eng, videos, class_of_video, lambda *a: self._support_sequences(eng, *a))
+        return self._add_shots(eng, videos, class_of_video, lambda *a: self._support_sequences(eng, *a), "add_shots")
 
     def add_shots_features(self, feats, class_of_video):
         """add_shots of clips whose tower features feats [Nv, T, E] fp32 (device) exist already; the tower does not run."""
@@ -443,6 +485,185 @@ class LiveGallery(_GalleryBase):
         in their order, no prototype moves.  layout_version rises.  Unknown ids raise before anything changes."""
         ids = [c.item() if isinstance(c, torch.Tensor) else c for c in (ids.reshape(-1).cpu() if isinstance(ids, torch.Tensor) else ids)]
         self._install(plan_remove(self._book, ids, self._name).book)
+        if self._ledger is not None:                          # their ledger slots are free again
+            self._lbook = ldg.drop_classes(self._lbook, ids)
+
+    # ------------------------------------------------------------------ the shot ledger (ledger=ShotLedger(...); clip_fsar_amd.ledger)
+    # The host half is ledger.LedgerBook and its planners.  An adding call checks the room when it is planned (_ledger_room: a call
+    # that StreamPool.enroll_windows plans in two parts on a book of its own is counted as one), takes its slots and serials in
+    # _update_sequences (_ledger_plan_put) and, with per_class, drops what is over the cap once its book is installed (_ledger_evict).
+    def _need_ledger(self, what, features=False):
+        if self._ledger is None:
+            raise ValueError("%s.%s: this gallery keeps no shot ledger (build it with ledger=ShotLedger(...))" % (self._name, what))
+        if features and not self._ledger.features:
+            raise ValueError("%s.%s: this ledger keeps no tower rows (build it with ShotLedger(features=True))" % (self._name, what))
+
+    def _ledger_room(self, base, planned, counts):
+        """an adding call of `counts` {class: shots}, planned from the Book `base` (None: the gallery's) into `planned`, fits the store"""
+        if self._ledger is None:
+            return
+        if base is None or base is self._book:                # a call starts: no Book from before an eviction is still to come
+            self._lcapped = set()
+        before = self._lpending[1] if self._lpending is not None and self._lpending[0] is base else 0
+        need = before + ldg.room_needed(self._lbook, counts, self._ledger.per_class)
+        ldg.check_room(self._lbook, need, self._name)
+        self._lpending = (planned, need)
+
+    def _ledger_forget(self):
+        """nothing of an earlier adding call is pending, evicted or last"""
+        self._lpending, self._levicted, self._last_shots, self._lcapped = None, {}, [], set()
+
+    def _ledger_stores(self):
+        if self._lstore is None:
+            f = dict(device=self.dev, dtype=torch.float32)
+            rows = self._rows() if self.merge_before else self.T          # the rows cfsl_accumulate sums for a shot
+            self._lstore = {"addends": torch.empty(self._ledger.shots, rows, self.E, **f)}
+            if self._ledger.features:
+                self._lstore["features"] = torch.empty(self._ledger.shots, self.T, self.E, **f)
+            self._ltables = ldhip.table_uploader(self.dev, TABLE_ROWS)
+        return self._lstore
+
+    def _ledger_plan_put(self, classes, rows, origin):
+        """the serials and slots of the call's shots -> (the PutPlan, the slots [Nv] int32 on the device, class-grouped as the sequences
+        are; None when no shot of the call is kept).  Nothing of the ledger changes before _ledger_install_put."""
+        plan = ldg.plan_put(self._lbook, [(c, r[2]) for c, r in zip(classes, rows)], origin, self._ledger.per_class, self._name)
+        if all(s < 0 for s in plan.slots):
+            return plan, None
+        self._ledger_stores()
+        return plan, torch.tensor(plan.slots, device=self.dev, dtype=torch.int32)
+
+    def _ledger_install_put(self, plan):
+        """the ledger's book of an adding call whose device work is queued"""
+        self._lbook, self._lpending = plan.book, None
+        self._last_shots, self._levicted = plan.serials, plan.evicted
+
+    def _ledger_evict(self, eng):
+        """Behind the install of an adding call's Book.  per_class: the classes the call took over their cap are re-summed from the
+        shots they keep.  And a ledgered class has as many shots as its list says: a Book that was planned before an earlier part of the
+        same call evicted (StreamPool.enroll_windows plans its two gallery calls up front) still carries the count from before."""
+        if self._ledger is None:
+            return
+        classes, self._levicted = list(self._levicted), {}
+        self._lcapped.update(classes)
+        lists, have = self._lbook.lists, self._book.shots
+        wrong = {c: len(lists[c]) for c in self._lcapped if c in lists and c in have and have[c] != len(lists[c])}
+        if wrong:
+            shots = dict(have)
+            shots.update(wrong)
+            self._book = self._book._replace(shots=shots)
+        if classes:
+            self._resum_classes(eng, classes)
+
+    def _last_in_video_order(self, ids_of_video, classes):
+        """_last_shots, made class-grouped, in the order of the call's videos"""
+        if self._ledger is None:
+            return
+        local = {c: i for i, c in enumerate(classes)}
+        order = sorted(range(len(ids_of_video)), key=lambda v: (local[ids_of_video[v]], v))
+        by_video = [None] * len(order)
+        for at, v in enumerate(order):
+            by_video[v] = self._last_shots[at]
+        self._last_shots = by_video
+
+    def _resum_classes(self, eng, classes):
+        """sums, prototypes and norms of ledgered classes again from the addends their lists name, in that order: one cfld_resum launch
+        per TABLE_ROWS classes, then the gallery's own path as after add_shots"""
+        st, book, T, E = self._store, self._lbook, self.T, self.E
+        lst = self._ledger_stores()
+        self._touch_slots([self._book.slot_of[c] for c in classes])
+        for c0 in range(0, len(classes), TABLE_ROWS):
+            part = classes[c0:c0 + TABLE_ROWS]
+            rows, slots = ldg.resum_rows(book, part, self._book.slot_of)
+            table = self._ltables.upload([list(r) for r in rows])
+            slot_list = torch.tensor(slots, device=self.dev, dtype=torch.int32)
+            if self.merge_before:
+                seqs = torch.empty(len(part), T + 1, E, device=self.dev, dtype=torch.float32)
+                ldhip.resum(lst["addends"], slot_list, st["sums"], seqs, table, by_slot=False)
+                self._prototypes_of_means(eng, seqs, [r[0] for r in rows])
+            else:
+                ldhip.resum(lst["addends"], slot_list, st["sums"], st["P"], table, by_slot=True)
+            lhip.slot_norms(st["P"], st["pn"], self._upload([(r[0], 0, 1, 0) for r in rows]))
+
+    @property
+    def last_shots(self):
+        """serials of the shots the most recent adding call made, in its video order (StreamPool.enroll_windows: in the order of its
+        items, whichever of its two gallery calls made them).  A shot that per_class dropped at once has a serial too."""
+        self._need_ledger("last_shots")
+        return list(self._last_shots)
+
+    def shot_list(self, cid):
+        """[Shot(serial, class_id, origin)] of a registered class, oldest first; empty for an unledgered class"""
+        self._need_ledger("shot_list")
+        if cid not in self._book.slot_of:
+            raise ValueError("%s: class %r is not registered (shot_list)" % (self._name, cid))
+        return [ldg.Shot(s, cid, self._lbook.origin_of[s]) for s in self._lbook.lists.get(cid, ())]
+
+    def _serials(self, serials):
+        return [s.item() if isinstance(s, torch.Tensor) else s for s in (serials.reshape(-1).cpu() if isinstance(serials, torch.Tensor)
+                                                                        else serials)]
+
+    def remove_shots(self, serials):
+        """The shots leave their classes: every touched class's sum is formed again from its remaining addends in their order, its
+        prototype and norms follow; the tower does not run.  Returns the touched classes' shot counts, in first-appearance order.  The
+        touched slots' revisions rise; generations, columns and layout_version stay.  An unknown or repeated serial, a class's last shot
+        and a shot of an unledgered class raise before anything changes."""
+        self._need_ledger("remove_shots")
+        eng = self._fresh_engine()
+        plan = ldg.plan_drop(self._lbook, self._serials(serials), self._name)
+        shots = dict(self._book.shots)
+        shots.update((c, len(plan.book.lists[c])) for c in plan.classes)
+        self._lbook, self._book = plan.book, self._book._replace(shots=shots)
+        self._resum_classes(eng, plan.classes)
+        return [shots[c] for c in plan.classes]
+
+    def shot_features(self, serial):
+        """the [T, E] tower rows of a shot, a copy (a ledger with features=True)"""
+        self._need_ledger("shot_features", features=True)
+        if serial not in self._lbook.slot_of:
+            raise ValueError("%s: %r is not the serial of a ledgered shot (shot_features)" % (self._name, serial))
+        return self._lstore["features"][self._lbook.slot_of[serial]].clone()
+
+    def move_shots(self, serials, target):
+        """remove_shots(serials), then add_shots_features of their tower rows to the registered class `target`: the shots join it as its
+        newest, in the order given, under new serials (returned).  Everything that can be refused is refused before anything changes."""
+        self._need_ledger("move_shots", features=True)
+        serials = self._serials(serials)
+        ldg.plan_drop(self._lbook, serials, self._name)
+        plan_shots(self._book, [target] * len(serials), self._name)       # the removal frees the room the shots take again
+        feats = self._lstore["features"].index_select(0, torch.tensor([self._lbook.slot_of[s] for s in serials], device=self.dev))
+        self.remove_shots(serials)
+        self.add_shots_features(feats, [target] * len(serials))
+        return self.last_shots
+
+    def shot_fits(self, classes=None):
+        """{class id: [(serial, fit)]} of ledgered classes (None: every one, in column order): fit is the mean over the T rows of the
+        cosine between the shot's addend and the sum of the others of its class (NaN for a class of one shot).  One launch per
+        TABLE_ROWS classes, one synchronisation."""
+        self._need_ledger("shot_fit")
+        book = self._lbook
+        if classes is None:
+            classes = [c for c in self._book.order if c in book.lists]
+        else:
+            classes = _registered(self._book, classes, self._name, "shot_fit")
+            if len(set(classes)) != len(classes):
+                raise ValueError("%s: a class appears twice in shot_fit: %r" % (self._name, classes))
+            for c in classes:
+                ldg.ledgered(book, c, "shot_fit", self._name)
+        if not classes:
+            return {}
+        lst, outs = self._ledger_stores(), []
+        for c0 in range(0, len(classes), TABLE_ROWS):
+            rows, slots = ldg.resum_rows(book, classes[c0:c0 + TABLE_ROWS], self._book.slot_of)
+            out = torch.empty(len(slots), device=self.dev, dtype=torch.float32)
+            ldhip.fit(lst["addends"], self._store["sums"], torch.tensor(slots, device=self.dev, dtype=torch.int32), out,
+                      self._ltables.upload([list(r) for r in rows]), self.T)
+            outs.append(out)
+        fits = iter(torch.cat(outs).cpu().tolist())
+        return {c: [(s, next(fits)) for s in book.lists[c]] for c in classes}
+
+    def shot_fit(self, cid):
+        """[(serial, fit)] of one ledgered class, oldest first: shot_fits([cid])[cid]"""
+        return self.shot_fits([cid])[cid]
 
     # ------------------------------------------------------------------ classification
     def _columns(self, classes):
@@ -599,8 +820,61 @@ class LiveGallery(_GalleryBase):
         else:
             P, pn = torch.empty(0, self.T, self.E), torch.empty(0)
             text, sums = torch.empty(0, self.E), torch.empty(0, self._rows(), self.E)
-        return {"fingerprint": self.fingerprint(), "class_ids": list(book.order), "prototypes": P, "norms": pn, "text": text, "sums": sums,
-                "counts": [book.shots[c] for c in book.order]}
+        sd = {"fingerprint": self.fingerprint(), "class_ids": list(book.order), "prototypes": P, "norms": pn, "text": text, "sums": sums,
+              "counts": [book.shots[c] for c in book.order]}
+        if self._ledger is not None:
+            sd["ledger"] = self._ledger_state()
+        return sd
+
+    def _ledger_state(self):
+        """the "ledger" key of state_dict: the shots of the ledgered classes, class by class in column order, oldest first"""
+        lb = self._lbook
+        serials = [s for c in self._book.order for s in lb.lists.get(c, ())]
+        led = {"serials": serials, "class_ids": [lb.class_of[s] for s in serials], "origins": [lb.origin_of[s] for s in serials],
+               "next_serial": lb.next_serial, "addends": None, "features": None}
+        rows = self._rows() if self.merge_before else self.T
+        idx = torch.tensor([lb.slot_of[s] for s in serials], device=self.dev, dtype=torch.long)
+        for key, r in (("addends", rows),) + ((("features", self.T),) if self._ledger.features else ()):
+            led[key] = self._lstore[key].index_select(0, idx).cpu() if serials else torch.empty(0, r, self.E)
+        return led
+
+    def _load_ledger(self, led, ids, counts):
+        """the ledger of a loaded state: its shots into the slots 0 .. n-1 in the state's order.  A class is ledgered when the state
+        holds exactly its count of shots; every other class (all of them for a state without "ledger") is unledgered."""
+        name = "LiveGallery.load_state_dict"
+        lb = ldg.new_ledger_book(self._ledger.shots, self._lbook.next_serial)
+        if led is None:
+            self._ledger_forget()
+            self._lbook = lb._replace(unledgered=frozenset(ids))
+            return
+        serials, cls, origins = list(led["serials"]), list(led["class_ids"]), list(led["origins"])
+        n, rows = len(serials), self._rows() if self.merge_before else self.T
+        if len(cls) != n or len(origins) != n or len(set(serials)) != n or any(o not in ldg.ORIGINS for o in origins):
+            raise ValueError("%s: the ledger's serials, class ids and origins do not agree" % name)
+        if n > self._ledger.shots:
+            raise ValueError("%s: the state's ledger holds %d shots, this gallery's ShotLedger(shots=%d)" % (name, n, self._ledger.shots))
+        if tuple(led["addends"].shape) != (n, rows, self.E):
+            raise ValueError("%s: the ledger's addends have shape %s, expected %s" % (name, tuple(led["addends"].shape), (n, rows, self.E)))
+        if self._ledger.features and (led.get("features") is None or tuple(led["features"].shape) != (n, self.T, self.E)):
+            raise ValueError("%s: this gallery's ledger keeps tower rows (features=True), the state's has none of shape %s" % (
+                name, (n, self.T, self.E)))
+        self._ledger_forget()                                               # every refusal is behind us
+        lists = {}
+        for s, c in zip(serials, cls):
+            lists.setdefault(c, []).append(s)
+        have = dict(zip(ids, counts))
+        good = {c for c, l in lists.items() if have.get(c, 0) == len(l)}
+        keep = [i for i in range(n) if cls[i] in good]
+        if keep:
+            lst = self._ledger_stores()
+            idx = torch.tensor(keep, dtype=torch.long)
+            for key in ("addends", "features") if self._ledger.features else ("addends",):
+                lst[key][:len(keep)].copy_(led[key].index_select(0, idx).to(device=self.dev, dtype=torch.float32))
+        at = {serials[i]: j for j, i in enumerate(keep)}
+        self._lbook = lb._replace(free=list(range(len(keep), lb.cap)), next_serial=max([lb.next_serial, int(led.get("next_serial", 0))] +
+                                                                                   [s + 1 for s in serials]),
+                                  slot_of=at, class_of={serials[i]: cls[i] for i in keep}, origin_of={serials[i]: origins[i] for i in keep},
+                                  lists={c: lists[c] for c in good}, unledgered=frozenset(c for c in ids if c not in good))
 
     def load_state_dict(self, sd):
         """a LiveGallery's or a SupportGallery's state.  Classes without sums (a SupportGallery's) score normally and take no further shots."""
@@ -624,6 +898,8 @@ class LiveGallery(_GalleryBase):
         if len(set(ids)) != C:
             raise ValueError("LiveGallery.load_state_dict: a class id appears twice")
         self._bind()
+        if self._ledger is not None:                          # (raises on a ledger that does not fit before the store is written)
+            self._load_ledger(sd.get("ledger"), ids, counts if sums is not None else [0] * C)
         old_version = self._book.version
         book = new_book(max(self._capacity, C, self._store_cap() if self._store is not None else 0))
         if C:

@@ -89,9 +89,9 @@ class LiveTextGallery(LiveGallery):
         shots.update(dict.fromkeys(new_ids, 0))               # plan_add counts a shot each: here a class has none
         return trows, [0] * len(new_ids), plan._replace(book=plan.book._replace(shots=shots))
 
-    def _register_sequences(self, eng, trows, counts, plan, sequences):
+    def _register_sequences(self, eng, trows, counts, plan, sequences, origin="enroll"):
         if self.mode == "combine":
-            return super()._register_sequences(eng, trows, counts, plan, sequences)
+            return super()._register_sequences(eng, trows, counts, plan, sequences, origin)
         st = self._ensure_store(plan.book.cap)                # the sequences are not made: nothing reads them
         self._write_text_rows(st, plan.slots, trows)
         C0 = len(self._book.order)

@@ -1608,13 +1608,25 @@ class StreamPool:
                                                        [(plan.positions[i] + shift) % self.cap for i in order],
                                                        [local[ids[i]] for i in order], *at_tempo), offs)
 
-        result = {}
+        result, serial_of = {}, {}
+
+        def made(members, classes):
+            """a gallery with a shot ledger: the serials its call just made, class-grouped as the sequences were, by item"""
+            if getattr(g, "_ledger", None) is not None:
+                local = {c: j for j, c in enumerate(classes)}
+                serial_of.update(zip(sorted(members, key=lambda i: (local[ids[i]], i)), g._last_shots))
+
         if known:
             result.update(zip(shot_plan.classes, g._shots_sequences(eng, shot_plan, sequences(known, shot_plan.classes))))
+            made(known, shot_plan.classes)
         if new:
             trows, counts, add_plan = add
             g._register_sequences(eng, trows, counts, add_plan, sequences(new, new_ids))
             result.update(zip(new_ids, counts))
+            made(new, new_ids)
+        if serial_of:                                         # last_shots: of the whole call, in the order of its items
+            g._last_shots = [serial_of[i] for i in range(len(items))]
+            result.update((c, g.shots(c)) for c in result)    # per_class: the counts the call leaves behind
         return {c: result[c] for c in dict.fromkeys(ids)}
 
     def enroll(self, h, class_id, window=None, text=None, join=False, tempo=None):
