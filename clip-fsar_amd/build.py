@@ -220,11 +220,13 @@ def build_addon(name, force: bool = False, verbose: bool = True) -> str:
 # still= (clip_fsar_amd.still): frames that did not change skip the tower, and the contest of a stream pool with contest=
 # (clip_fsar_amd.contest): only a window's leading classes reach the detector, and the history search of a stream pool with history=
 # (clip_fsar_amd.history): a class's best non-overlapping occurrences in the windows a store that outlives the ring still holds, and
-# the shot ledger of a live gallery with ledger= (clip_fsar_amd.ledger): every shot's addend kept, so that shots leave, move and are audited.
+# the shot ledger of a live gallery with ledger= (clip_fsar_amd.ledger): every shot's addend kept, so that shots leave, move and are audited,
+# and the timeline of a stream pool with timeline= (clip_fsar_amd.timeline): every push's class scores folded into buckets of windows
+# -- peak, its window, a count above a level -- that outlive the ring.
 # ExtLib values again; the open registry.
 PLUGIN_LIBS = {name: ExtLib(os.path.join(EXT, name + ".hip"), os.path.join(os.path.dirname(HERE), "include", "ext", "clipfsar_%s.h" % name),
                             os.path.join(HERE, "libclipfsar_%s.so" % name), os.path.join(HERE, "build", name, "resource_usage.json"))
-               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still", "contest", "history", "ledger")}
+               for name in ("baseline", "shortlist", "pool_select", "align", "tempo", "evidence", "still", "contest", "history", "ledger", "timeline")}
 
 
 def plugin_lib_names() -> list:

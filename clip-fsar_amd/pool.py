@@ -42,6 +42,8 @@
     y = StreamPool(live_gallery, stride=2, history=History(frames=4096))                                  # clip_fsar_amd.history
     y.searchable(a); r = y.search([7, "kite"], top=16); r.hits[7]     # [Hit(session, class_id, window, score, tempo)], best first
     y.hit_features(hit); y.explain_hit(hit); y.enroll_hit(hit, "kite")                # on a hit whose window the history still holds
+    d = StreamPool(live_gallery, timeline=Timeline(span=16, buckets=256, level=0.6))                      # clip_fsar_amd.timeline
+    d.timeline(a).peak; d.recall([7, "kite"], top=16).hits[7]         # [buckets, C] per-bucket peaks; [Hit(..)] of the best buckets
 
 clip_fsar_amd.stream.WindowStream serves a fixed set of streams that advance in lockstep.  Here every session numbers its own frames from 0
 at open() or reset(): window k of a session holds its frames k * stride + j * rate, j = 0 .. T-1, and is emitted once, in order, by the push
@@ -142,6 +144,16 @@ local maxima within `separation` windows of one session -- a local-maximum filte
 window -- and of those the `top` highest across sessions.  It synchronises once, to read the hit records.  hit_features, explain_hit and
 enroll_hit read a hit's window out of the store the way enroll and explain read the ring.  The option adds nothing to stats().
 
+timeline=Timeline(span, buckets, level, of) (clip_fsar_amd.timeline, which states the buckets, the cells and the fold; a LiveGallery or
+LiveTextGallery): every push that completes a window also runs one launch (libclipfsar_timeline.so, clip_fsar_amd.timeline_hip) over
+the judged scores -- after smoothing and the baseline, before the contest; or the plane `of` names -- over the table, keys and
+generations every keyed launch of the push takes, the sessions' first window numbers riding in the same upload: per (session, bucket of
+`span` windows, class) the peak score, the peak's window and the count of windows at or above `level`, in cells [max_streams, buckets,
+store capacity] keyed and guarded like the class mode's, a ring of `buckets` buckets per pair.  The push returns the bits it returns
+without the option.  timeline(h) reads a session's held buckets (one launch, no synchronisation); recall(classes, ...) reads the held
+buckets of the sessions asked for into a plane of bucket peaks and runs the history's peak search on it: hours of scores in three
+launches and no scoring, its hits' windows the pool's own.  shortlist= is refused.  The option adds nothing to stats().
+
 Enrolment: a session's ring holds the tower rows of its last cap frames, and a support sequence is T tower rows plus the class's text row.
 enroll / enroll_windows turn windows that are still in the ring into shots (libclipfsar_enroll.so, clip_fsar_amd.enroll_hip: one copy
 launch per kind, new classes and further shots) and hand the sequences to the LiveGallery's registration from sequences.  Nothing of the
@@ -168,6 +180,7 @@ from . import pool_hip as php
 from . import pool_select_hip as pship
 from . import still_hip as skhip
 from . import tempo_hip as tphip
+from . import timeline_hip as tlhip
 from .baseline import Baseline
 from .contest import Contest
 from .events import EventRule, translate
@@ -178,6 +191,7 @@ from .history import (History, Hit, SearchResult, check_min_score, check_separat
 from .ingest import FrameIngest
 from .still import StillGate, plan_still
 from .stream import StreamOutput, window_plan
+from .timeline import RecallHit, RecallResult, Timeline, TimelineView, held_buckets, read_rows
 
 PackedOutput = collections.namedtuple("PackedOutput", "sessions first_window offsets logits smoothed")
 # Of a push in which a session has a class list of its own: logits is flat, session i owning [logit_offsets[i], logit_offsets[i + 1]) as
@@ -412,11 +426,45 @@ class _Cells:
         return self.planes
 
 
+class _Buckets:
+    """_Cells' sibling with a ring of B buckets between the two keys: the timeline's planes [max_streams, B, store capacity] -- peak
+    fp32, at, above and marks int32 --, made by the first push that folds.  The marks are the guard: made zero-filled, a grown store's
+    new columns zero, and the planes [slot] of the slots in `forgotten` zeroed by the next use; the others are read behind it alone."""
+
+    def __init__(self, dev, max_streams, B):
+        self.dev, self.max_streams, self.B = dev, max_streams, B
+        self.planes = None
+        self.forgotten = set()
+
+    @staticmethod
+    def too_many(max_streams, B, cap):
+        return ("StreamPool: timeline= keeps a state cell per (session slot, bucket, store slot): max_streams = %d x buckets = %d x "
+                "store capacity = %d is 2^31 or more -- build the pool with fewer streams or buckets or the gallery with fewer slots"
+                % (max_streams, B, cap))
+
+    def at(self, cap):
+        if self.max_streams * self.B * cap > tlhip.MAX_CELLS:
+            raise ValueError(self.too_many(self.max_streams, self.B, cap))
+        old = None if self.planes is None else self.planes[0].shape[2]
+        if old != cap:
+            f32, i32 = torch.float32, torch.int32
+            new = tuple((torch.zeros if i == 3 else torch.empty)(self.max_streams, self.B, cap, device=self.dev, dtype=dtype)
+                        for i, dtype in enumerate((f32, i32, i32, i32)))
+            if old is not None:
+                for t, was in zip(new, self.planes):
+                    t[:, :, :old].copy_(was)
+            self.planes = new
+        for slot in sorted(self.forgotten):
+            self.planes[3][slot].zero_()
+        self.forgotten.clear()
+        return self.planes
+
+
 class StreamPool:
     def __init__(self, gallery, max_streams=64, stride=1, rate=1, max_push=64, smooth=0.0, ingest=None, smooth_by="column",
                  *positional, shortlist=None, shortlist_hold=None, rates=None, evidence=None, still=None, contest=None, history=None,
-                 events=None, baseline=None):
-        # shortlist=, shortlist_hold=, rates=, evidence=, still=, contest= and history= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
+                 timeline=None, events=None, baseline=None):
+        # shortlist=, shortlist_hold=, rates=, evidence=, still=, contest=, history= and timeline= are keyword-only.  events and baseline were the 9th and 10th positional parameters before the two
         # existed and still are: `positional` takes them, so no earlier call changes its meaning.
         if len(positional) > 2 or (positional and events is not None) or (len(positional) > 1 and baseline is not None):
             raise TypeError("StreamPool: at most 10 positional arguments (.., smooth_by, events, baseline), and neither of the last two "
@@ -476,6 +524,8 @@ class StreamPool:
                                  "the detector; build the pool with events=EventRule(...) as well")
         if history is not None:
             self._check_history(gallery, history, (gallery.T - 1) * rate + max_push, max_streams)
+        if timeline is not None:
+            self._check_timeline(gallery, timeline, max_streams, shortlist, smooth_by == "class" and bool(smooth), baseline)
         if baseline is not None:
             if not isinstance(baseline, Baseline):
                 raise TypeError("StreamPool: baseline must be a Baseline, got %s" % type(baseline).__name__)
@@ -568,6 +618,13 @@ class StreamPool:
             self._hs_tables = php.TableUploader(self.dev, 2 * max_streams)   # a round's two tables in one upload; a search's one
             self._hs_X = None                    # a search's gathered windows [rows, T, E], grown on demand
             self._hs_work = None                 # history_hip.peaks' workspace, grown on demand
+        self._timeline = timeline                # the Timeline, or None: nothing below is there
+        if timeline is not None:
+            self._tl_cells = _Buckets(self.dev, max_streams, timeline.buckets)      # (peak, at, above, marks), made by the first fold
+            self._stores.append(self._tl_cells)  # open() and reset() queue the slot's marks for zeroing
+            self._tl_first = None                # the push's first window numbers, behind its table in the one upload
+            self._tl_tables = None               # timeline() and recall(): the read's table and the peak search's, made by the first call
+            self._tl_work = None                 # history_hip.peaks' workspace of recall(), grown on demand
         if ingest is not None and not isinstance(ingest, FrameIngest):
             raise TypeError("StreamPool: ingest must be a FrameIngest, got %s" % type(ingest).__name__)
         if ingest is not None:
@@ -598,6 +655,24 @@ class StreamPool:
             raise ValueError("StreamPool: rates= together with shortlist= is not supported -- tempo windows of a shortlisted pool are out "
                              "of scope; build the pool with one of the two")
         return tuple(rates)
+
+    @staticmethod
+    def _check_timeline(gallery, timeline, max_streams, shortlist, by_class, baseline):
+        """every refusal of timeline= of the constructor, before anything is allocated"""
+        if not isinstance(timeline, Timeline):
+            raise TypeError("StreamPool: timeline must be a Timeline, got %s" % type(timeline).__name__)
+        if not hasattr(gallery, "slot_generations"):
+            raise ValueError("StreamPool: timeline= needs a gallery with a slot store (a LiveGallery or a LiveTextGallery), not a %s"
+                             % type(gallery).__name__)
+        if shortlist is not None:
+            raise ValueError("StreamPool: timeline= together with shortlist= is not supported -- a shortlist's columns change with "
+                             "every push, a timeline over them is out of scope; build the pool with one of the two")
+        for of, made, how in (("smoothed", by_class, "smooth > 0 and smooth_by=\"class\""), ("deviation", baseline is not None, "baseline=")):
+            if timeline.of == of and not made:
+                raise ValueError("StreamPool: timeline.of = %r names a plane this pool does not make -- build it with %s, or leave of at "
+                                 "None" % (of, how))
+        if max_streams * timeline.buckets * gallery.capacity > tlhip.MAX_CELLS:
+            raise ValueError(_Buckets.too_many(max_streams, timeline.buckets, gallery.capacity))
 
     @staticmethod
     def _check_history(gallery, history, cap, max_streams):
@@ -988,6 +1063,8 @@ class StreamPool:
         deviation = None
         if self._baseline is not None:
             judged = deviation = self._normalize(cp, judged)
+        if cp is not None and self._timeline is not None:                             # before the contest: its plane is the detector's alone
+            self._fold(cp, {None: judged, "logits": logits, "smoothed": smoothed, "deviation": deviation}[self._timeline.of])
         if cp is not None and self._events is not None:
             seen = judged if self._contest_rule is None else self._contest(cp, judged)     # the detector alone sees the demoted plane
             self._detect(handles, recs, first_window, seen, cp, columns, [s.t + n for s, n in zip(recs, counts)], tempo)
@@ -1015,6 +1092,8 @@ class StreamPool:
         if self._smooth_keys[0] != key or self._smooth_keys[1] is not every:
             own = torch.tensor(plan.keys, device=self.dev, dtype=torch.int32) if key else None
             self._smooth_keys = (key, every, own if every is None else every if own is None else torch.cat([every, own]))
+        if self._timeline is not None:
+            return plan, gens, self._smooth_keys[2], self._timeline_tables(plan.rows, recs)
         if self._smooth_tables is None:
             self._smooth_tables = cship.table_uploader(self.dev, self.max_streams)
         return plan, gens, self._smooth_keys[2], self._smooth_tables.upload(plan.rows)
@@ -1034,7 +1113,7 @@ class StreamPool:
     @property
     def _keyed(self):
         """whether a push runs a launch over (session slot, store slot) cells, i.e. needs _class_push's plan and upload"""
-        return self._by_class or self._events is not None or self._baseline is not None
+        return self._by_class or self._events is not None or self._baseline is not None or self._timeline is not None
 
     def _normalize(self, cp, scores):
         """the push's session-major scores (dense [NW, C] or the grouped layout) -> their deviations in the same layout; one
@@ -1841,3 +1920,154 @@ class StreamPool:
             return list(g.add_shots_features(feats, [cid]))[0]
         g.add_classes_features(feats, [cid], text)
         return 1
+
+    # ------------------------------------------------------------------ timeline
+    def _timeline_tables(self, rows, recs):
+        """_class_push's upload of a pool with timeline=: the push's table, and behind it -- in the same upload, six to a row -- the
+        first window number of every row's session (its frame counter has not moved yet) -> the table as upload(rows) gives it; the
+        first numbers wait in _tl_first for _fold"""
+        S, cols = len(rows), cship.TABLE_COLS
+        if self._smooth_tables is None:
+            self._smooth_tables = cship.table_uploader(self.dev, self.max_streams + -(-self.max_streams // cols))
+        first = [window_plan(s.t, 0, self.T, self.stride, self.rate)[0] for s in recs]
+        first += [0] * (-len(first) % cols)
+        both = self._smooth_tables.upload(rows + [first[i:i + cols] for i in range(0, len(first), cols)])
+        self._tl_first = cship.Table(both.host[S:].view(-1)[:S], both.dev[S:].view(-1)[:S], S)
+        return cship.Table(both.host[:S], both.dev[:S], S)
+
+    def _fold(self, cp, scores):
+        """one cftl_fold over the push's session-major plane `scores` (dense [NW, C] or the grouped layout), on the table and keys
+        every keyed launch of the push takes: no synchronisation, nothing returned"""
+        tl = self._timeline
+        _, gens, keys, table = cp
+        tlhip.fold(scores.view(-1), *self._tl_cells.at(gens.shape[0]), gens, keys, table, self._tl_first, tl.span, tl.level)
+
+    def _need_timeline(self, what):
+        if self._timeline is None:
+            raise ValueError("StreamPool.%s: this pool keeps no timeline (build it with timeline=Timeline(...))" % what)
+
+    def _held_buckets(self, s, last, what):
+        """the buckets the timeline still holds of a session, from the host's counters"""
+        if last is not None and (isinstance(last, bool) or not isinstance(last, int) or last < 1):
+            raise ValueError("StreamPool.%s: last must be None or an integer >= 1 (buckets), got %r" % (what, last))
+        tl = self._timeline
+        return held_buckets(window_plan(0, s.t, self.T, self.stride, self.rate)[1], tl.span, tl.buckets, last)
+
+    def _read_buckets(self, slots, buckets, K, keys):
+        """one cftl_read: the buckets `buckets[i]` (a range) of slot slots[i] over the K store slots `keys` (a device list, shared by
+        every row) -> (peak, at, above), each [sum of the ranges' lengths, K] on the device, the rows one after the other"""
+        rows, n_out = read_rows(slots, buckets, [K] * len(slots), [0] * len(slots))
+        peak = torch.empty(n_out // K, K, device=self.dev, dtype=torch.float32)
+        at = torch.empty(n_out // K, K, device=self.dev, dtype=torch.int32)
+        above = torch.empty_like(at)
+        if n_out:
+            if self._tl_tables is None:
+                self._tl_tables = (tlhip.read_uploader(self.dev, self.max_streams), php.TableUploader(self.dev, self.max_streams))
+            gens = self.gallery.slot_generations()
+            tlhip.read(*self._tl_cells.at(gens.shape[0]), gens, keys, peak.view(-1), at.view(-1), above.view(-1),
+                       self._tl_tables[0].upload(rows), self._timeline.span)
+        return peak, at, above
+
+    def timeline(self, h, classes=None, last=None):
+        """What the session saw, bucket by bucket -> TimelineView(first_bucket, span, class_ids, peak, at, above): row i of the planes
+        [nb, K] (on the device; fp32, int32, int32) is bucket first_bucket + i, the windows (first_bucket + i) * span + 0 .. span - 1,
+        and holds per class the bucket's highest score, the window it belongs to and the count of windows at or above the timeline's
+        level -- (-inf, -1, 0) where the pair has no live cell (clip_fsar_amd.timeline states the rule).  The buckets are those still
+        held, max(0, bn - B + 1) .. bn with bn the bucket of the session's newest window; last=n: the newest n of them; a session
+        without a window gives empty planes.  classes: ids of the session's columns, in the order given; None: all of them, in their
+        order.  One cftl_read, no synchronisation; changes nothing."""
+        self._need_timeline("timeline")
+        what = "StreamPool.timeline"
+        s = self._session(h)
+        g = self.gallery
+        from .live_gallery import plan_columns
+        if classes is None:
+            ids = list(g._book.order if s.classes is None else s.classes)
+            plan_columns(g._book, ids or None, what)
+        else:
+            ids = list(classes) if isinstance(classes, (list, tuple)) else None
+            if ids is None:
+                raise TypeError("%s: classes must be None or a list of registered class ids, got %s" % (what, type(classes).__name__))
+            plan_columns(g._book, ids, what)
+            for c in ids:
+                if s.classes is not None and c not in s.classes:
+                    raise ValueError("%s: class %r is not registered (classes= of session %d)" % (what, c, h))
+        buckets = self._held_buckets(s, last, "timeline")
+        K = len(ids)
+        if not len(buckets) or not K:
+            empty = lambda dtype: torch.empty(0, K, device=self.dev, dtype=dtype)
+            return TimelineView(buckets.start, self._timeline.span, tuple(ids), empty(torch.float32), empty(torch.int32), empty(torch.int32))
+        keys = g._columns(None) if classes is None and s.classes is None else \
+            torch.tensor([g._book.slot_of[c] for c in ids], device=self.dev, dtype=torch.int32)
+        return TimelineView(buckets.start, self._timeline.span, tuple(ids), *self._read_buckets([s.slot], [buckets], K, keys))
+
+    def recall(self, classes, sessions=None, top=16, min_score=None, separation=1, last=None):
+        """When were `classes` (1 to 64 registered ids, no repeats) strongest, in the buckets the timeline still holds?  -> RecallResult:
+        hits {class id: [Hit(session, class_id, window, score, tempo=None)], best first} -- window the peak's own window, so a hit goes
+        into explain / enroll while the ring holds it and, on a pool with history=, into hit_features / explain_hit / enroll_hit; each
+        hit also carries .bucket and .above --, peaks {class id: the count before top cut it}, buckets scanned.  The rule is
+        clip_fsar_amd.history.reference_search on the plane of bucket peaks, session-major in the order of `sessions` (None: every open
+        session in handle order), buckets ascending: `separation` counts buckets, min_score and top are search()'s.  last=n: the newest
+        n buckets of every session.  One cftl_read, the two launches of the history's peak search, a gather; one synchronisation.
+        Nothing is scored, and nothing changes."""
+        self._need_timeline("recall")
+        what = "StreamPool.recall"
+        g = self.gallery
+        from .live_gallery import plan_columns
+        ids = list(classes) if isinstance(classes, (list, tuple)) else None
+        if ids is None:
+            raise TypeError("%s: classes must be a list of registered class ids, got %s" % (what, type(classes).__name__))
+        slots = plan_columns(g._book, ids, what)
+        if len(ids) > hship.MAX_CLASSES:
+            raise ValueError("%s: %d classes -- one recall takes 1 to %d; split the list" % (what, len(ids), hship.MAX_CLASSES))
+        if sessions is None:
+            handles = self.sessions
+        else:
+            handles = list(sessions) if isinstance(sessions, (list, tuple)) else None
+            if handles is None:
+                raise TypeError("%s: sessions must be None or a list of open sessions, got %s" % (what, type(sessions).__name__))
+            if len(set(handles)) != len(handles):
+                raise ValueError("%s: a session appears twice in sessions=: %r" % (what, handles))
+        recs = [self._session(h) for h in handles]
+        check_top(top, what)
+        floor = check_min_score(min_score, what)
+        sep = check_separation(separation, what)
+        buckets = [self._held_buckets(s, last, "recall") for s in recs]
+        counts = [len(b) for b in buckets]
+        NB, K = sum(counts), len(ids)
+        sep = device_separation(sep, counts, what)
+        if NB * K > hship.MAX_PLANE:
+            raise ValueError("%s: %d buckets x %d classes -- a plane holds at most 2^30 scores; recall fewer sessions or classes, or "
+                             "give last=" % (what, NB, K))
+        if not NB:                                 # nothing is held (or no session is open): nothing is launched
+            return RecallResult({c: [] for c in ids}, {c: 0 for c in ids}, 0)
+        keys = torch.tensor(slots, device=self.dev, dtype=torch.int32)
+        peak, at, above = self._read_buckets([s.slot for s in recs], buckets, K, keys)
+        offsets = [0]
+        for n in counts:
+            offsets.append(offsets[-1] + n)
+        table = self._tl_tables[1].upload([[s.slot, 0, 0, 0, 0, n, off, 0] for s, n, off in zip(recs, counts, offsets)])
+        # the records in one buffer, so that one copy brings them down: n_hits [K], n_peaks [K], then [K, top] each of hit_rows,
+        # hit_scores, the hits' windows and their counts
+        buf = torch.empty(2 * K + 4 * K * top, device=self.dev, dtype=torch.int32)
+        n_hits, n_peaks = buf[:K], buf[K:2 * K]
+        part = lambda i: buf[2 * K + i * K * top:2 * K + (i + 1) * K * top].view(K, top)
+        hit_rows, hit_scores = part(0), part(1).view(torch.float32)
+        work = self._work("_tl_work", hship.workspace_words(NB, K))
+        hship.peaks(peak, work, hit_rows, hit_scores, n_hits, n_peaks, table, sep, floor, top)
+        where = hit_rows.clamp(max=NB - 1).long().t()                                # [top, K]: an unused place reads the last row
+        part(2).copy_(at.gather(0, where).t())
+        part(3).copy_(above.gather(0, where).t())
+        host = buf.cpu()                           # the recall's one synchronisation
+        n, peaks = host[:K].tolist(), host[K:2 * K].tolist()
+        hpart = lambda i: host[2 * K + i * K * top:2 * K + (i + 1) * K * top].view(K, top)
+        rows, values = hpart(0).tolist(), hpart(1).view(torch.float32).tolist()
+        windows, aboves = hpart(2).tolist(), hpart(3).tolist()
+        owner = [i for i, m in enumerate(counts) for _ in range(m)]                  # plane row -> its session's place in the recall
+        hits = {}
+        for k, c in enumerate(ids):
+            order = sorted(range(n[k]), key=lambda j: (-values[k][j], rows[k][j]))   # descending score, then plane row
+            hits[c] = [RecallHit(handles[owner[rows[k][j]]], c, windows[k][j], values[k][j], None,
+                                 bucket=buckets[owner[rows[k][j]]].start + rows[k][j] - offsets[owner[rows[k][j]]], above=aboves[k][j])
+                       for j in order]
+        return RecallResult(hits, dict(zip(ids, peaks)), NB)
